@@ -17,11 +17,21 @@ coords_grid - U[0, 64) per pixel, a fresh draw per iteration.
 
 value = stereo pairs/s through the corr path, all ranks (weak scaling: every
 rank processes its own batch of 8; the path shards by pair with no collective).
-The end-to-end model (encoders/GRU on PyTorch ops) is not in this number; it
-is reported beside it (``e2e``), and so is the row-sharded full network of
-BASELINE configs[3] (``config4_network``: 1984x2880, 32 iterations, GRU halo
-exchange over RCCL in the timed region).  ``--config middlebury --network``
-makes that network rate the line's ``value``.
+
+A plain run does only what that figure needs: inputs, W warm-up steps, the K
+timed steps, the result line (``ms_per_step`` = wall milliseconds of one timed
+step).  ``--dump-outputs DIR`` also writes what the last timed step returned
+to its caller as ``DIR/<name>.npy`` (float32); the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
+
+``--full`` adds every side measurement to the line: the kernel-level split
+and rooflines of a step (instrumented passes of their own), the per-step
+latency distribution, the corr-path backward and the upsampler, the host CPU
+baseline, the end-to-end model (``e2e``: encoders/GRU on PyTorch ops, not in
+``value``) and the row-sharded full network of BASELINE configs[3]
+(``config4_network``: 1984x2880, 32 iterations, GRU halo exchange over RCCL
+in the timed region).  ``--config middlebury --network`` makes that network
+rate the line's ``value``.
 """
 import argparse
 import json
@@ -41,6 +51,7 @@ import pkgload  # noqa: E402
 
 pkgload.load()
 from raft_stereo_amd import CorrBlock1D, _lib, coords_grid  # noqa: E402
+from raft_stereo_amd.corr import auto_layout  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec
 HBM_ACHIEVABLE_GBS = 6290.0    # the same guide's measured float4 copy (report both)
@@ -495,7 +506,34 @@ def leg_watchdog(result, rank, limit):
     return t
 
 
-def row_sharded_network(device, rank, world, steps, warmup, iters=32, image_hw=(1984, 2880)):
+DUMP_CAP_BYTES = 64 << 20      # all the files of one --dump-outputs run together
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_output(dirname, name, tensor, rank, share):
+    """--dump-outputs: ``tensor`` as ``dirname/<name>.npy`` (rank 0; other
+    ranks ``<name>.rank<r>.npy``) in float32, logical (C) element order.  An
+    array of more than ``share`` bytes is written as a fixed sample instead:
+    its elements at ``share // 4`` flat indices drawn with DUMP_SAMPLE_SEED
+    (same shape => same indices), in ascending index order.  Returns the
+    entry of the result line's ``dumped`` for this file."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    t = tensor.detach().float()
+    entry = {"file": (name if rank == 0 else f"{name}.rank{rank}") + ".npy",
+             "shape": list(t.shape), "dtype": "float32"}
+    if t.numel() * 4 > share:
+        k = share // 4
+        g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+        idx = torch.randint(t.numel(), (k,), generator=g).sort().values
+        t = t.reshape(-1)[idx.to(t.device)]
+        entry.update({"sampled": k, "sample_seed": DUMP_SAMPLE_SEED})
+    np.save(os.path.join(dirname, entry["file"]), t.cpu().numpy())
+    return entry
+
+
+def row_sharded_network(device, rank, world, steps, warmup, iters=32, image_hw=(1984, 2880),
+                        outputs=None):
     """BASELINE configs[3] end to end: ONE synthetic full-resolution pair,
     RAFTStereo (seeded random-init weights, fp32, eval) row-sharded over the
     ``world`` ranks by ``shard.RowShardedStereo`` -- encoders on each rank's
@@ -503,7 +541,9 @@ def row_sharded_network(device, rank, world, steps, warmup, iters=32, image_hw=(
     the corr path on its rows, the GRU loop with its per-conv halo exchanges
     (point-to-point; RCCL over xGMI when the group is nccl) -- 32 iterations.
     Every exchange is inside the timed region.  Timed as the MAX over ranks
-    of the barrier-bracketed wall time (strong scaling: one pair per step)."""
+    of the barrier-bracketed wall time (strong scaling: one pair per step).
+    ``outputs``: a dict that receives the last timed step's final disparity
+    (this rank's rows, on the host) as ``outputs["disparity"]``."""
     from raft_stereo_amd.network import RAFTStereo, StereoArgs
     from raft_stereo_amd.shard import RowShardedStereo
     torch.manual_seed(0)
@@ -535,6 +575,8 @@ def row_sharded_network(device, rank, world, steps, warmup, iters=32, image_hw=(
     r0, r1 = rs._own_rows(RowShardedStereo._heights(H, model.args.n_downsample,
                                                     model.args.n_gru_layers), hz)
     flow_rows = int(preds[-1].shape[2])
+    if outputs is not None:
+        outputs["disparity"] = preds[-1].float().cpu()
     unsharded = None
     if world == 1:
         # the plain RAFTStereo on the same pair: the N=1 baseline every
@@ -571,6 +613,15 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="sceneflow", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (kernel split, rooflines, latency, backward, "
+                         "upsampler, e2e, config-4 network, CPU baseline) and add them to the line; "
+                         "the options that tune or skip them (--no-cpu-baseline, --cpu-seconds, "
+                         "--e2e-steps, --no-backward, --config4-steps, --config4-timeout, --pmc) "
+                         "apply only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32; a "
+                         "fixed seeded sample of an array above the size cap)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--graph", action="store_true",
@@ -625,6 +676,8 @@ def main():
         args.layout = "auto" if args.config in BF16_CONFIGS else "rows"
     if args.network and args.config != "middlebury":
         ap.error("--network applies to --config middlebury")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the timed steps)")
     shadow = (None if args.shadow == "default" else () if args.shadow == "none"
               else tuple(int(v) for v in args.shadow.split(",")))
 
@@ -683,7 +736,6 @@ def main():
     else:
         f1, f2, coords = make_inputs(cfg, device, seed=1 + rank,
                                      dtype=torch.bfloat16 if bf16 else torch.float32, field=args.field)
-    P = B * H * W1
 
     def step(ev=None):
         if ev is not None:
@@ -709,7 +761,7 @@ def main():
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                step()
+                graph_out = step()
         torch.cuda.synchronize()
 
         def run(ev=None):
@@ -719,6 +771,7 @@ def main():
             graph.replay()
             if ev is not None:
                 ev[2].record()
+            return graph_out    # the captured step's output buffer, rewritten by every replay
 
     with torch.no_grad():
         for _ in range(args.warmup):
@@ -731,12 +784,168 @@ def main():
         # tools/graph_floor.py)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for k in range(args.steps):
+        for k in range(args.steps - 1):
             run()
+        last = run()        # the last step's output, kept for --dump-outputs
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         t1 = time.perf_counter()
+    dumped = {}
+    dump_share = DUMP_CAP_BYTES // (world * (2 if args.network else 1))
+    if args.dump_outputs:
+        # what a caller of the timed path holds after its last step: the last
+        # lookup's correlation features
+        dumped["corr_out"] = dump_output(args.dump_outputs, "corr_out", last, rank, dump_share)
+    del last
+    elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device=device)
+    if world > 1:
+        dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
+    sec = float(elapsed.item())
+    ms_per_step = 1e3 * sec / args.steps
+    # pairs the whole job processed per step: one row-sharded pair, the global
+    # batch, or B per rank (weak scaling)
+    job_pairs = 1 if row_shard else (CONFIGS[args.config][0] if global_batch else world * B)
+    if proj:
+        # one GPU ran only rank 0's share: value counts the work that ran (B
+        # pairs, or the row share of one pair); the N-rank rate is reported
+        # under "projection" only
+        run_pairs = (r1 - r0) / CONFIGS[args.config][2] if row_shard else B
+    else:
+        run_pairs = job_pairs
+    value = run_pairs * args.steps / sec
+    # the layout the step's blocks resolved to (CorrBlock1D's own rule, host side only)
+    pyramid_layout = args.layout
+    if pyramid_layout == "auto":
+        pyramid_layout = auto_layout(f1, f2, L, r, shadow=shadow, exact_f32=args.exact_f32,
+                                     low_latency=args.config in LOW_LATENCY_CONFIGS)
+
+    result = {
+        "metric": "stereo pairs/s at 540x960, 32 iters, 1-8 GPUs; corr-lookup HBM GB/s",
+        "value": value,
+        "unit": "pairs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong" if ((row_shard or global_batch) and not proj) else "weak",
+        "vs_baseline": None,
+        "dtype": "bf16" if bf16 else "f32",
+        "data": ("synthetic (randn fmaps, coords_grid - U[0,64) per iteration)" if args.field == "random"
+                 else f"synthetic (randn fmaps, coords_grid - a {args.field} disparity field in [0,64))"),
+        "config": {"workload": desc + (" (HIP graph replay)" if args.graph else "")
+                   + (f" (rows sharded over {world} ranks)" if row_shard else ""),
+                   "config": args.config, "global_batch": run_pairs,
+                   "fmap": [B, D, H, W1], "W2": W2, "levels": L, "radius": r, "iters": iters,
+                   "parallelism": (f"row-shard x{world}" if row_shard else f"batch-shard x{world}"),
+                   "corr_out_layout": "channels_last" if args.channels_last else "nchw",
+                   "pyramid_layout": pyramid_layout, "coords_field": args.field},
+        "full": args.full,
+    }
+    if args.dump_outputs:
+        result["dumped"] = dumped       # a --network run adds its disparity below
+    pmc = {}
+    if args.full:
+        details, pmc = corr_path_details(args, (B, D, H, W1, W2, L, r, iters), bf16, shadow,
+                                         run, f1, f2, coords)
+        result.update(details)
+    if args.full and not args.no_backward and args.config == "sceneflow":
+        result["backward"] = backward_timing(cfg, f1, f2, coords)
+        bw = result["backward"]
+        for key, us in (("roofline_lookup_bwd", "lookup_bwd_calls_us"),
+                        ("roofline_lookup_bwd_per_call", "lookup_bwd_us")):
+            rl = bw.get(key)
+            if rl is None:
+                continue
+            bname, bpmc = pmc_entry(pmc, rl["kernel"].split("<")[0])
+            if bpmc.get("hbm_bytes"):   # PMC bytes the kernel really moves, per launch
+                rl["kernel"] = bname
+                rl["traffic"] = bpmc["hbm_bytes"]
+                rl["traffic_gbs"] = rl["traffic"] / (bw[us] * 1e-6) / 1e9
+                rl["traffic_frac"] = rl["traffic_gbs"] / HBM_PEAK_GBS
+                rl["traffic_over_algorithmic"] = rl["traffic"] / rl["algorithmic_bytes"]
+        rv = result["backward"]["roofline_volume_bwd"]
+        vbname, vbpmc = pmc_entry(pmc, rv["kernel"].split("<")[0])
+        if "mfma_util" in vbpmc:    # the exact instance the backward ran (one per config)
+            rv["kernel"] = vbname
+            rv["mfma_util_pmc"] = vbpmc["mfma_util"]
+        result["upsample"] = upsample_timing(cfg, device)
+    if args.full and args.e2e_steps > 0 and args.config == "sceneflow":
+        result["e2e"] = e2e_pairs_per_s(cfg, device, args.e2e_steps, 1, world=world)
+        result["e2e"]["corr_path_share"] = (ms_per_step / result["e2e"]["ms_per_batch"])
+    if args.full and args.e2e_steps > 0 and args.config == "realtime":
+        # C5 is latency-bound: whole network per pair, with and without the
+        # loop's coords update + flow fused into the lookup (SURVEY 8f rank 4)
+        result["e2e"] = {
+            "unfused": e2e_pairs_per_s(cfg, device, max(args.e2e_steps, 10), 3, (480, 640)),
+            "fused_step": e2e_pairs_per_s(cfg, device, max(args.e2e_steps, 10), 3, (480, 640),
+                                          fuse_step=True)}
+    if proj:
+        # one GPU ran rank 0's share of a proj-GPU job: the rate proj such
+        # ranks reach when nothing is exchanged (batch shards; the corr path of
+        # row shards).  A projection from measured per-rank work, not a
+        # multi-GPU measurement.
+        result["projection"] = {
+            "per_rank_of": proj, "rank_share": ({"rows": [r0, r1]} if row_shard else {"batch": B}),
+            "projected_ms_per_step": ms_per_step,
+            "projected_value": job_pairs / (ms_per_step * 1e-3),
+            "projected_global_batch": job_pairs,
+            "note": "single GPU timing rank 0's share; no collective in the timed path; "
+                    "projected_value assumes every rank takes as long -- not a measurement "
+                    "of N GPUs (the line's value is the work that ran, per second)"}
+        result["config"]["parallelism"] = f"rank 0 of {proj} (single-GPU projection input)"
+    # BASELINE configs[3] end to end: in the default --full run as a side leg
+    # (so an N-GPU run of it measures config 4's scaling too), or as the
+    # line's value with --config middlebury --network
+    net_steps = (max(args.steps, 1) if args.network else
+                 args.config4_steps if args.full and args.config == "sceneflow" and not proj else 0)
+    if net_steps > 0 and not args.network:
+        # the side leg must not take the corr-path line down with it: an error
+        # (e.g. from RCCL, which raises on every rank alike) is recorded in
+        # the line instead, and a leg that has not finished after
+        # --config4-timeout seconds (a hung exchange) prints the line without
+        # it and ends every rank with status 0
+        dog = leg_watchdog(result, rank, args.config4_timeout)
+        try:
+            result["config4_network"] = row_sharded_network(device, rank, world, net_steps, 1)
+        except Exception as e:  # noqa: BLE001
+            result["config4_network"] = {"error": f"{type(e).__name__}: {e}"[:600]}
+        dog.cancel()
+    elif net_steps > 0:
+        net_out = {} if args.dump_outputs else None
+        leg = row_sharded_network(device, rank, world, net_steps, max(args.warmup, 1), outputs=net_out)
+        if net_out:     # the network is this line's timed path: its final disparity too
+            dumped["disparity"] = dump_output(args.dump_outputs, "disparity", net_out["disparity"],
+                                              rank, dump_share)
+        result["corr_path"] = {k: result[k] for k in ("value", "ms_per_step", "config")}
+        result.update({
+            "value": leg["pairs_per_s"], "ms_per_step": leg["ms_per_pair"],
+            "steps": net_steps, "warmup": leg["warmup"], "scaling": "strong",
+            "network": leg,
+            "config": {"workload": "BASELINE configs[3]: full RAFTStereo network, one "
+                                   "1984x2880 pair, 32 iterations, fp32, image rows sharded "
+                                   f"over {world} rank(s) (encoders with per-module halos, "
+                                   "corr path on own rows, GRU per-conv halo exchange)",
+                       "config": "middlebury", "global_batch": 1, "image": [1984, 2880],
+                       "iters": 32, "parallelism": f"row-shard x{world}"}})
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        result["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds,
+                                              full=args.config == "sceneflow")
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def corr_path_details(args, dims, bf16, shadow, run, f1, f2, coords):
+    """--full: the kernel-level split of the timed step (build / lookups, from
+    instrumented passes of their own), the per-step latency distribution and
+    the rooflines.  Returns (fields of the result line, the PMC entries of
+    this config)."""
+    B, D, H, W1, W2, L, r, iters = dims
+    P = B * H * W1
+    with torch.no_grad():
         # kernel-level split of a step (build / lookups) from a second,
         # instrumented pass: events on the launch stream (torch's current
         # stream, which CorrBlock1D launches on)
@@ -796,22 +1005,6 @@ def main():
             torch.cuda.synchronize()
             lat.append((time.perf_counter() - a0) * 1e3)
     lat.sort()
-    elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device=device)
-    if world > 1:
-        dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
-    sec = float(elapsed.item())
-    ms_per_step = 1e3 * sec / args.steps
-    # pairs the whole job processed per step: one row-sharded pair, the global
-    # batch, or B per rank (weak scaling)
-    job_pairs = 1 if row_shard else (CONFIGS[args.config][0] if global_batch else world * B)
-    if proj:
-        # one GPU ran only rank 0's share: value counts the work that ran (B
-        # pairs, or the row share of one pair); the N-rank rate is reported
-        # under "projection" only
-        run_pairs = (r1 - r0) / CONFIGS[args.config][2] if row_shard else B
-    else:
-        run_pairs = job_pairs
-    value = run_pairs * args.steps / sec
 
     vflops = volume_flops(B, D, H, W1, W2)
     s_el = 2 if bf16 else 4
@@ -883,27 +1076,7 @@ def main():
         roof_lookup["pmc_source"] = f"{os.path.relpath(args.pmc, ROOT)} [{args.config}] {pmc.get('tag', '')}"
     dominant = roof_lookup if lookup_ms * iters >= build_ms else roof_volume
 
-    result = {
-        "metric": "stereo pairs/s at 540x960, 32 iters, 1-8 GPUs; corr-lookup HBM GB/s",
-        "value": value,
-        "unit": "pairs/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "strong" if ((row_shard or global_batch) and not proj) else "weak",
-        "vs_baseline": None,
-        "dtype": "bf16" if bf16 else "f32",
-        "data": ("synthetic (randn fmaps, coords_grid - U[0,64) per iteration)" if args.field == "random"
-                 else f"synthetic (randn fmaps, coords_grid - a {args.field} disparity field in [0,64))"),
-        "config": {"workload": desc + (" (HIP graph replay)" if args.graph else "")
-                   + (f" (rows sharded over {world} ranks)" if row_shard else ""),
-                   "config": args.config, "global_batch": run_pairs,
-                   "fmap": [B, D, H, W1], "W2": W2, "levels": L, "radius": r, "iters": iters,
-                   "parallelism": (f"row-shard x{world}" if row_shard else f"batch-shard x{world}"),
-                   "corr_out_layout": "channels_last" if args.channels_last else "nchw",
-                   "pyramid_layout": blk.layout, "coords_field": args.field},
+    details = {
         "roofline": dominant,
         "roofline_volume": roof_volume,
         "roofline_lookup": roof_lookup,
@@ -930,88 +1103,7 @@ def main():
                   f"per-level lookup: the build writes the levels a lookup reads, {written}; "
                   "level num_levels is pooled only when corr_pyramid is read"),
     }
-    if not args.no_backward and args.config == "sceneflow":
-        result["backward"] = backward_timing(cfg, f1, f2, coords)
-        bw = result["backward"]
-        for key, us in (("roofline_lookup_bwd", "lookup_bwd_calls_us"),
-                        ("roofline_lookup_bwd_per_call", "lookup_bwd_us")):
-            rl = bw.get(key)
-            if rl is None:
-                continue
-            bname, bpmc = pmc_entry(pmc, rl["kernel"].split("<")[0])
-            if bpmc.get("hbm_bytes"):   # PMC bytes the kernel really moves, per launch
-                rl["kernel"] = bname
-                rl["traffic"] = bpmc["hbm_bytes"]
-                rl["traffic_gbs"] = rl["traffic"] / (bw[us] * 1e-6) / 1e9
-                rl["traffic_frac"] = rl["traffic_gbs"] / HBM_PEAK_GBS
-                rl["traffic_over_algorithmic"] = rl["traffic"] / rl["algorithmic_bytes"]
-        rv = result["backward"]["roofline_volume_bwd"]
-        vbname, vbpmc = pmc_entry(pmc, rv["kernel"].split("<")[0])
-        if "mfma_util" in vbpmc:    # the exact instance the backward ran (one per config)
-            rv["kernel"] = vbname
-            rv["mfma_util_pmc"] = vbpmc["mfma_util"]
-        result["upsample"] = upsample_timing(cfg, device)
-    if args.e2e_steps > 0 and args.config == "sceneflow":
-        result["e2e"] = e2e_pairs_per_s(cfg, device, args.e2e_steps, 1, world=world)
-        result["e2e"]["corr_path_share"] = (ms_per_step / result["e2e"]["ms_per_batch"])
-    if args.e2e_steps > 0 and args.config == "realtime":
-        # C5 is latency-bound: whole network per pair, with and without the
-        # loop's coords update + flow fused into the lookup (SURVEY 8f rank 4)
-        result["e2e"] = {
-            "unfused": e2e_pairs_per_s(cfg, device, max(args.e2e_steps, 10), 3, (480, 640)),
-            "fused_step": e2e_pairs_per_s(cfg, device, max(args.e2e_steps, 10), 3, (480, 640),
-                                          fuse_step=True)}
-    if proj:
-        # one GPU ran rank 0's share of a proj-GPU job: the rate proj such
-        # ranks reach when nothing is exchanged (batch shards; the corr path of
-        # row shards).  A projection from measured per-rank work, not a
-        # multi-GPU measurement.
-        result["projection"] = {
-            "per_rank_of": proj, "rank_share": ({"rows": [r0, r1]} if row_shard else {"batch": B}),
-            "projected_ms_per_step": ms_per_step,
-            "projected_value": job_pairs / (ms_per_step * 1e-3),
-            "projected_global_batch": job_pairs,
-            "note": "single GPU timing rank 0's share; no collective in the timed path; "
-                    "projected_value assumes every rank takes as long -- not a measurement "
-                    "of N GPUs (the line's value is the work that ran, per second)"}
-        result["config"]["parallelism"] = f"rank 0 of {proj} (single-GPU projection input)"
-    # BASELINE configs[3] end to end: in the default run as a side leg (so an
-    # N-GPU run of the default command measures config 4's scaling too), or as
-    # the line's value with --config middlebury --network
-    net_steps = (max(args.steps, 1) if args.network else
-                 args.config4_steps if args.config == "sceneflow" and not proj else 0)
-    if net_steps > 0 and not args.network:
-        # the side leg must not take the corr-path line down with it: an error
-        # (e.g. from RCCL, which raises on every rank alike) is recorded in
-        # the line instead, and a leg that has not finished after
-        # --config4-timeout seconds (a hung exchange) prints the line without
-        # it and ends every rank with status 0
-        dog = leg_watchdog(result, rank, args.config4_timeout)
-        try:
-            result["config4_network"] = row_sharded_network(device, rank, world, net_steps, 1)
-        except Exception as e:  # noqa: BLE001
-            result["config4_network"] = {"error": f"{type(e).__name__}: {e}"[:600]}
-        dog.cancel()
-    elif net_steps > 0:
-        leg = row_sharded_network(device, rank, world, net_steps, max(args.warmup, 1))
-        result["corr_path"] = {k: result[k] for k in ("value", "ms_per_step", "config")}
-        result.update({
-            "value": leg["pairs_per_s"], "ms_per_step": leg["ms_per_pair"],
-            "steps": net_steps, "warmup": leg["warmup"], "scaling": "strong",
-            "network": leg,
-            "config": {"workload": "BASELINE configs[3]: full RAFTStereo network, one "
-                                   "1984x2880 pair, 32 iterations, fp32, image rows sharded "
-                                   f"over {world} rank(s) (encoders with per-module halos, "
-                                   "corr path on own rows, GRU per-conv halo exchange)",
-                       "config": "middlebury", "global_batch": 1, "image": [1984, 2880],
-                       "iters": 32, "parallelism": f"row-shard x{world}"}})
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        result["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds,
-                                              full=args.config == "sceneflow")
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+    return details, pmc
 
 
 if __name__ == "__main__":

@@ -26,7 +26,7 @@ rocm-smi --showproductname > "$OUT/gpu.txt" 2>&1 || true
 has tsplit && step pytest_split 600 python -u -m pytest tests/test_split_gpu.py tests/test_configs_gpu.py -v -rf --timeout 120 --timeout-method thread
 has test  && step pytest_gpu 900 python -u -m pytest tests -m gpu -v -rf --timeout 120 --timeout-method thread ${PYTEST_K:+-k "$PYTEST_K"}
 has smoke && step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-has bench && step bench 600 python bench.py
+has bench && step bench 600 python bench.py --full
 has e2e && step e2e_probe 900 python tools/e2e_probe.py
 has probe && step line_probe 300 python tools/line_probe.py
 has lprobe && step lookup_probe 300 python tools/lookup_probe.py --dev-variants ${LPROBE_VARIANTS:-201,202}
@@ -36,14 +36,14 @@ has ablate && step ablate 600 python tools/ablate.py --build-modes 0 --lookup-va
 has ablateb && step ablate_bwd 600 python tools/ablate.py --build-modes 0 --lookup-variants 0 --bwd
 has ablatec && step ablate_conv 600 python tools/ablate.py --build-modes 0 --lookup-variants 0 --convc1
 has ablatek && step ablate_kitti 600 python tools/ablate.py --config kitti --build-modes 0,2,1,3 --lookup-variants 0,1,3
-has configs && step bench_realtime 300 python bench.py --config realtime --no-cpu-baseline --steps 50 --warmup 5 && step bench_realtime_graph 300 python bench.py --config realtime --graph --no-cpu-baseline --steps 200 --warmup 10
-has configs && step bench_middlebury 300 python bench.py --config middlebury --no-cpu-baseline --steps 5 --warmup 2
-has configs && step bench_kitti 300 python bench.py --config kitti --no-cpu-baseline --steps 10 --warmup 3
+has configs && step bench_realtime 300 python bench.py --full --config realtime --no-cpu-baseline --steps 50 --warmup 5 && step bench_realtime_graph 300 python bench.py --full --config realtime --graph --no-cpu-baseline --steps 200 --warmup 10
+has configs && step bench_middlebury 300 python bench.py --full --config middlebury --no-cpu-baseline --steps 5 --warmup 2
+has configs && step bench_kitti 300 python bench.py --full --config kitti --no-cpu-baseline --steps 10 --warmup 3
 has ab16 && step ablate_b16 600 python tools/ablate.py --config kitti --build-modes ${AB16_MODES:-0,49,50,40,51} --lookup-variants 0 --rounds 5
-has kitti && step bench_kitti 300 python bench.py --config kitti --no-cpu-baseline --steps 10 --warmup 3
+has kitti && step bench_kitti 300 python bench.py --full --config kitti --no-cpu-baseline --steps 10 --warmup 3
 if has profk; then
     step rocprof_kitti 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/profk" -o trace \
-        -- python3 bench.py --config kitti --steps 10 --warmup 3 --no-cpu-baseline --e2e-steps 0
+        -- python3 bench.py --full --config kitti --steps 10 --warmup 3 --no-cpu-baseline --e2e-steps 0
     find "$OUT/profk" -name "*stats*.csv" -exec sh -c 'echo "== $1"; cat "$1"' _ {} \; > "$OUT/kernel_stats_kitti.txt" 2>/dev/null
     head -c 2000 "$OUT/kernel_stats_kitti.txt"
 fi
@@ -57,7 +57,7 @@ if has pmck; then   # kitti build HBM bytes (profiles/traffic.json "kitti")
 fi
 if has prof; then
     step rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o trace \
-        -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --e2e-steps 0 --config4-steps 0
+        -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --e2e-steps 0 --config4-steps 0
     find "$OUT/prof" -name "*stats*.csv" -exec sh -c 'echo "== $1"; cat "$1"' _ {} \; > "$OUT/kernel_stats.txt" 2>/dev/null
     head -c 3000 "$OUT/kernel_stats.txt"
 fi
@@ -111,39 +111,39 @@ if has pmcl; then   # lookup variants: L1->L2 request count / latency, L2 hits, 
 fi
 if has proj; then   # per-rank shapes at N = 1/2/4/8 on one GPU (projection inputs)
     for N in 1 2 4 8; do
-        step proj_kitti_$N 300 python bench.py --config kitti --per-rank-of $N --no-cpu-baseline --steps 10 --warmup 3
-        step proj_middlebury_$N 300 python bench.py --config middlebury --per-rank-of $N --no-cpu-baseline --steps 5 --warmup 2
+        step proj_kitti_$N 300 python bench.py --full --config kitti --per-rank-of $N --no-cpu-baseline --steps 10 --warmup 3
+        step proj_middlebury_$N 300 python bench.py --full --config middlebury --per-rank-of $N --no-cpu-baseline --steps 5 --warmup 2
     done
 fi
 has shardt && step pytest_shard 600 python -u -m pytest tests/test_shard_gpu.py -v -rf --timeout 300 --timeout-method thread
 # bench.py --gpus 2 without a launcher (self-launch), 2 ranks sharing cuda:0 over gloo
-has launch && step launch_gloo2 600 env RAFTCORR_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline --e2e-steps 0 --no-backward
-has netmb && step net_middlebury_1 600 python bench.py --config middlebury --network --steps 2 --warmup 1 --no-cpu-baseline
-has netmb && step net_middlebury_gloo2 900 env RAFTCORR_BENCH_BACKEND=gloo python bench.py --gpus 2 --config middlebury --network --steps 1 --warmup 1 --no-cpu-baseline
+has launch && step launch_gloo2 600 env RAFTCORR_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline --e2e-steps 0 --no-backward
+has netmb && step net_middlebury_1 600 python bench.py --full --config middlebury --network --steps 2 --warmup 1 --no-cpu-baseline
+has netmb && step net_middlebury_gloo2 900 env RAFTCORR_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --config middlebury --network --steps 1 --warmup 1 --no-cpu-baseline
 has pconv && step shard_probe_perconv 900 python tools/shard_probe.py --perconv
 if has shadows; then   # config 2 / 4: level-0 shadow copy and NHWC output re-measured as whole steps
     BQ="--no-cpu-baseline --e2e-steps 0 --no-backward --config4-steps 0 --steps 20 --warmup 5"
     for rep in 1 2; do
-        step shadows_sf_default_$rep 300 python bench.py $BQ
-        step shadows_sf_02_$rep 300 python bench.py $BQ --shadow 0,2
-        step shadows_sf_cl_$rep 300 python bench.py $BQ --channels-last
-        step shadows_sf_02cl_$rep 300 python bench.py $BQ --shadow 0,2 --channels-last
-        step shadows_mb_default_$rep 300 python bench.py --config middlebury $BQ
-        step shadows_mb_02_$rep 300 python bench.py --config middlebury $BQ --shadow 0,2
+        step shadows_sf_default_$rep 300 python bench.py --full $BQ
+        step shadows_sf_02_$rep 300 python bench.py --full $BQ --shadow 0,2
+        step shadows_sf_cl_$rep 300 python bench.py --full $BQ --channels-last
+        step shadows_sf_02cl_$rep 300 python bench.py --full $BQ --shadow 0,2 --channels-last
+        step shadows_mb_default_$rep 300 python bench.py --full --config middlebury $BQ
+        step shadows_mb_02_$rep 300 python bench.py --full --config middlebury $BQ --shadow 0,2
     done
 fi
 if has shadowk; then   # config-3 shadow copies re-decided as whole steps
     for rep in 1 2; do
         for SH in default 2 none; do
-            step shadowk_b64_${SH}_$rep 300 python bench.py --config kitti --no-cpu-baseline --steps 10 --warmup 3 --shadow $SH
+            step shadowk_b64_${SH}_$rep 300 python bench.py --full --config kitti --no-cpu-baseline --steps 10 --warmup 3 --shadow $SH
         done
         for SH in default 0,2 none; do
-            step shadowk_b8_${SH/,/}_$rep 300 python bench.py --config kitti --per-rank-of 8 --no-cpu-baseline --steps 20 --warmup 5 --shadow $SH
+            step shadowk_b8_${SH/,/}_$rep 300 python bench.py --full --config kitti --per-rank-of 8 --no-cpu-baseline --steps 20 --warmup 5 --shadow $SH
         done
     done
 fi
 has rtab && step realtime_ab 300 python tools/realtime_ab.py ${RTAB_VARIANTS:-RAFTCORR_LOOKUP_VARIANT=6}
-has rtg && step bench_realtime_graph 300 python bench.py --config realtime --graph --no-cpu-baseline --steps 200 --warmup 10
+has rtg && step bench_realtime_graph 300 python bench.py --full --config realtime --graph --no-cpu-baseline --steps 200 --warmup 10
 has shard8 && step shard_probe_h8 900 python tools/shard_probe.py --halo 8
 has sablr && step build_ablate_realtime 300 python tools/build_ablate.py --config realtime --modes ${SABL_MODES:-0,4096} --rounds 9
 has sablm && step build_ablate_middlebury 300 python tools/build_ablate.py --config middlebury --modes ${SABL_MODES:-0,4096} --rounds 5
@@ -165,10 +165,10 @@ fi
 if has pmcjson; then   # profiles/pmc.json: three counter passes of bench.py itself per config
     for C in ${PMC_CONFIGS:-sceneflow kitti middlebury realtime}; do
         BA="--config $C --pmc-calibrate --steps 2 --warmup 1 --no-cpu-baseline --e2e-steps 0 --config4-steps 0"
-        step pmcj_${C}_f 180 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmcj_${C}_f" -o f -- python3 bench.py $BA
-        step pmcj_${C}_w 180 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmcj_${C}_w" -o w -- python3 bench.py $BA
+        step pmcj_${C}_f 180 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmcj_${C}_f" -o f -- python3 bench.py --full $BA
+        step pmcj_${C}_w 180 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmcj_${C}_w" -o w -- python3 bench.py --full $BA
         step pmcj_${C}_s 180 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES \
-            --output-format csv -d "$OUT/pmcj_${C}_s" -o s -- python3 bench.py $BA
+            --output-format csv -d "$OUT/pmcj_${C}_s" -o s -- python3 bench.py --full $BA
         python tools/pmc_collect.py $C "$OUT/pmcj_${C}_f" "$OUT/pmcj_${C}_w" "$OUT/pmcj_${C}_s" \
             --out "$OUT/pmc.json" --tag "$TAG" > "$OUT/pmcj_${C}.txt" 2>&1; cat "$OUT/pmcj_${C}.txt"
     done

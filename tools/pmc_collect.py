@@ -4,11 +4,11 @@
                                 [--tag r03]
 
 The three directories come from three separate passes of the SAME command
-(``bench.py --config <config> --pmc-calibrate ...``: the counters do not fit
-one pass), e.g.
+(``bench.py --full --config <config> --pmc-calibrate ...``: the counters do
+not fit one pass; ``--full`` so that the backward kernels run too), e.g.
 
-    rocprofv3 --pmc FETCH_SIZE -d <fetch_dir> -- python3 bench.py --config sceneflow --pmc-calibrate ...
-    rocprofv3 --pmc WRITE_SIZE -d <write_dir> -- python3 bench.py ...
+    rocprofv3 --pmc FETCH_SIZE -d <fetch_dir> -- python3 bench.py --full --config sceneflow --pmc-calibrate ...
+    rocprofv3 --pmc WRITE_SIZE -d <write_dir> -- python3 bench.py --full ...
     rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES -d <sq_dir> -- ...
 
 so every entry describes a kernel exactly as bench.py launches it for that
