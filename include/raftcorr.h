@@ -17,6 +17,8 @@
  *                   iteration in one launch.
  *   rc_convex_upsample  the convex upsampler for the mask the update block
  *                   produces.
+ *   rc_convex_upsample_backward  its gradient with respect to flow and mask,
+ *                   for a training loss on the full-resolution prediction.
  *   rc_corr_lookup_backward, rc_corr_build_backward  the gradient of the
  *                   path to the feature maps (autograd of model.py:267-326),
  *                   SURVEY.md §8f rank 2.
@@ -38,7 +40,7 @@
 extern "C" {
 #endif
 
-#define RC_ABI_VERSION 10
+#define RC_ABI_VERSION 11
 
 /* element types */
 #define RC_F32  0
@@ -314,6 +316,27 @@ int rc_corr_build_backward(const void *fmap1, const void *fmap2, int fmap_dtype,
  *   factor 1, 2, 4 or 8. */
 int rc_convex_upsample(const float *flow, const float *mask, int N, int C, int H, int W,
                        int factor, float *out, void *stream);
+
+/* Backward of rc_convex_upsample (ABI v11), for a loss taken on the
+ * full-resolution prediction.  With wt = the forward's softmax weights
+ * (recomputed from mask; nothing else is kept from the forward),
+ * nb[c][k] = f * flow[n][c][h + dy_k][w + dx_k] and g = grad_out:
+ *   grad_mask[n][k f^2 + i f + j][h][w] = wt_k * (d_k - sum_k' wt_k' d_k'),
+ *                        d_k = sum_c g[n][c][f h + i][f w + j] * nb[c][k]
+ *   grad_flow[n][c][y][x] = sum_k P[n][c][k][y - dy_k][x - dx_k],
+ *                        P[n][c][k][h][w] = f * sum_{i,j} wt_k * g[n][c][f h + i][f w + j]
+ *   (taps whose source pixel lies outside the image dropped).
+ *   flow, mask, grad_out: fp32 contiguous, the shapes of rc_convex_upsample's
+ *   flow, mask and out; grad_out aligned to min(16, 4 f) bytes.  grad_flow
+ *   (N,C,H,W) and grad_mask (N,9f^2,H,W) are overwritten; either may be NULL
+ *   and is then not computed (both NULL: RC_EINVAL).  workspace:
+ *   RC_UPSAMPLE_BWD_WS(N, C, H, W) floats holding P between the two launches,
+ *   required exactly when grad_flow != NULL.  factor 1, 2, 4 or 8.  No
+ *   atomics: every sum has a fixed order, so results repeat bit for bit. */
+#define RC_UPSAMPLE_BWD_WS(N, C, H, W) ((long long)(N) * (C) * 9 * (H) * (W))   /* floats */
+int rc_convex_upsample_backward(const float *flow, const float *mask, const float *grad_out,
+                                int N, int C, int H, int W, int factor,
+                                float *grad_flow, float *grad_mask, float *workspace, void *stream);
 
 #ifdef __cplusplus
 }

@@ -688,3 +688,28 @@ extern "C" int rc_convex_upsample(const float *flow, const float *mask, int N, i
                                             reinterpret_cast<hipStream_t>(stream)),
                   "rc_convex_upsample: launch");
 }
+
+extern "C" int rc_convex_upsample_backward(const float *flow, const float *mask, const float *grad_out,
+                                           int N, int C, int H, int W, int factor, float *grad_flow,
+                                           float *grad_mask, float *workspace, void *stream) {
+    g_err[0] = 0;
+    if (N < 0 || C < 1 || H < 0 || W < 0)
+        return fail(RC_EINVAL, "rc_convex_upsample_backward: bad shape N=%d C=%d H=%d W=%d", N, C, H, W);
+    if (factor != 1 && factor != 2 && factor != 4 && factor != 8)
+        return fail(RC_EUNSUPPORTED, "rc_convex_upsample_backward: factor %d (1, 2, 4 or 8)", factor);
+    if (!grad_flow && !grad_mask)
+        return fail(RC_EINVAL, "rc_convex_upsample_backward: neither grad_flow nor grad_mask requested");
+    if (grad_flow && !workspace)
+        return fail(RC_EINVAL, "rc_convex_upsample_backward: grad_flow needs a workspace of "
+                    "RC_UPSAMPLE_BWD_WS(N, C, H, W) floats");
+    if ((long long)N * H * W == 0) return RC_OK;
+    if (!flow || !mask || !grad_out) return fail(RC_EINVAL, "rc_convex_upsample_backward: null pointer");
+    // the kernel loads the f grad_out values of a sub-row as one vector
+    if (reinterpret_cast<uintptr_t>(grad_out) & (uintptr_t)(4 * std::min(factor, 4) - 1))
+        return fail(RC_EINVAL, "rc_convex_upsample_backward: grad_out must be %d-byte aligned",
+                    4 * std::min(factor, 4));
+    return hip_rc(rc_launch_convex_upsample_bwd(flow, mask, grad_out, N, C, H, W, factor, grad_flow,
+                                                grad_mask, workspace,
+                                                reinterpret_cast<hipStream_t>(stream)),
+                  "rc_convex_upsample_backward: launch");
+}

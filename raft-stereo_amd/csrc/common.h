@@ -243,3 +243,7 @@ bool rc_lookup_bwd_calls_fits(const rc::LookupBwdCallsArgs &a, int radius, int l
 hipError_t rc_launch_volume_bwd(const rc::BuildBwdArgs &a, hipStream_t s);
 hipError_t rc_launch_convex_upsample(const float *flow, const float *mask, int N, int C, int H,
                                      int W, int factor, float *out, hipStream_t s);
+// grad_flow / grad_mask may be null (not computed); workspace is read only with grad_flow
+hipError_t rc_launch_convex_upsample_bwd(const float *flow, const float *mask, const float *grad_out,
+                                         int N, int C, int H, int W, int factor, float *grad_flow,
+                                         float *grad_mask, float *workspace, hipStream_t s);

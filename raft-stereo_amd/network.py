@@ -280,7 +280,8 @@ class RAFTStereo(nn.Module):
         """Per-iteration low-resolution flow (the reference's D8 tail), or with
         ``upsample=True`` the full-resolution x-flow of each iteration through
         the convex upsampler (``upsample.convex_upsample``)
-        using the update block's mask (model.py:238-241, :264)."""
+        using the update block's mask (model.py:238-241, :264); differentiable
+        when grad is enabled."""
         a = self.args
         fmap1, fmap2, net_list, inp_list = self.features(image1, image2)
         corr_fn = self.corr_block(fmap1, fmap2, radius=a.corr_radius, num_levels=a.corr_levels)
@@ -332,5 +333,9 @@ class RAFTStereo(nn.Module):
         if upsample:
             from .upsample import convex_upsample
             f = 2 ** a.n_downsample
-            predictions = [convex_upsample(p[:, :1], m, f) for p, m in zip(predictions, masks)]
+            # with grad enabled every prediction carries the upsampler's backward
+            # (rc_convex_upsample_backward), so a loss can be taken on it
+            diff = torch.is_grad_enabled()
+            predictions = [convex_upsample(p[:, :1], m, f, differentiable=diff)
+                           for p, m in zip(predictions, masks)]
         return predictions
