@@ -21,6 +21,27 @@ static hipError_t dev_launch_build_split(const BuildArgs &a, long long nwg, int 
         // split once per workgroup into LDS planes (build_split_planes_kernel)
         return rc_launch_build_planes(const_cast<BuildArgs &>(a), s);
     }
+    // RAFTCORR_SPLIT_RING = 103 / 104: the full-width (128) ring with three /
+    // four slots on ANY row-layout shape, whatever the product's dispatch
+    // (sp_ring3) picks for it: 104 is the kernel every shape ran before the
+    // three-slot ring -- the yardstick of the A/B and of the bit-identity
+    // test.
+    if (!a.shk[0]) {
+        const int ring = dev_knob("RAFTCORR_SPLIT_RING");
+#define RC_SPLIT_RING_CASE(VAL, M, SLOTS)                                                                          \
+    if (ring == VAL) {                                                                                             \
+        if (a.nfused <= 3)                                                                                         \
+            hipLaunchKernelGGL((build_split_kernel<M, 3, 128, SLOTS>), dim3((unsigned)nwg), dim3(256), 0, s, a,    \
+                               (int)nwg, tf1, tf2, tiles1, tiles2);                                                \
+        else                                                                                                       \
+            hipLaunchKernelGGL((build_split_kernel<M, kSpMaxFused, 128, SLOTS>), dim3((unsigned)nwg), dim3(256),   \
+                               0, s, a, (int)nwg, tf1, tf2, tiles1, tiles2);                                       \
+        return hipGetLastError();                                                                                  \
+    }
+        RC_SPLIT_RING_CASE(103, 0, 3)
+        RC_SPLIT_RING_CASE(104, 0, 4)
+#undef RC_SPLIT_RING_CASE
+    }
     if (!a.shk[0] && a.nfused <= 3) {
         const int ring = dev_knob("RAFTCORR_SPLIT_RING");
         if (ring == 85 || ring == 87) {

@@ -30,7 +30,9 @@
 // epilogue_swapped).  Operand staging is the fp32 kernel's LDS-DMA ring
 // (volume.hip): 16-d stages of [16 d][128 w] fp32 for F1 and for F2, filled
 // by buffer_load ... lds with no VGPR staging, SL slots, one K step (32 d =
-// two stages) multiplied while the next is in flight.  Each DMA instruction
+// two stages) multiplied while the next is in flight (four slots, two
+// workgroups per CU), or one stage of it plus a mid-step refill (three slots,
+// three workgroups per CU: grids of more than two per CU).  Each DMA instruction
 // lands two 512-B rows; the blocks are 1040 B apart (16 B of padding) so the
 // two 16-lane halves of a fragment read (rows 8 apart) fall on different
 // banks.  Fragments are read in fp32 (lane (i, g): 8 consecutive d at one w,
@@ -55,6 +57,11 @@ struct SpCtx {
     // no per-stage 32-bit multiplies (8 % of the K loop's VALU issue)
     uint32_t oA[2], oB[2], sA, sB;
     int dr0;           // this lane's d row inside a stage, first instruction
+    // The three-slot kernel (at most 168 VGPRs) keeps one offset per operand
+    // and no row: its second instruction's rows lie two d further (dA / dB,
+    // uniform), and the lane's row is dlo or dlo + 1 with dlo uniform (odd)
+    uint32_t dA, dB;
+    bool odd;          // the lane fetches the second row of its 2-row block (d odd)
     bool wA, wB;       // the lane's 4 columns inside the tile extent
 };
 
@@ -62,18 +69,28 @@ struct SpCtx {
 // (TW / 2 lanes x 16 B: all 64 at TW = 128) per instruction -> 4 instructions
 // per stage.
 template <int MODE, int TW, int SL>
-__device__ __forceinline__ void sp_issue(const SpCtx &c, char *smem, int st) {
+__device__ __forceinline__ void sp_issue(const SpCtx &c, char *smem, int st, int slot) {
     typedef __attribute__((address_space(3))) void lds_void;
     using G = SpRing<TW, SL>;
-    char *sA = smem + (st % SL) * G::Slot, *sB = sA + G::Op;
+    char *sA = smem + slot * G::Slot, *sB = sA + G::Op;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int r0 = 4 * c.wave + 2 * i;
-        const int d = st * kSpBK + c.dr0 + 2 * i;
         // rows d >= D and columns past the tile extent are not fetched
         // (out-of-range offset)
-        uint32_t offA = d < c.D && c.wA ? c.oA[i] + (uint32_t)st * c.sA : 0xFFFFFF00u;
-        uint32_t offB = d < c.D && c.wB ? c.oB[i] + (uint32_t)st * c.sB : 0xFFFFFF00u;
+        uint32_t offA, offB;
+        if constexpr (SL == 3) {
+            // rem = D - dlo is uniform, so d < D is a scalar compare per half
+            // of the block
+            const int rem = c.D - (st * kSpBK + 4 * c.wave + 2 * i);
+            const bool dok = c.odd ? rem >= 2 : rem >= 1;
+            offA = dok && c.wA ? c.oA[0] + ((uint32_t)st * c.sA + (uint32_t)i * c.dA) : 0xFFFFFF00u;
+            offB = dok && c.wB ? c.oB[0] + ((uint32_t)st * c.sB + (uint32_t)i * c.dB) : 0xFFFFFF00u;
+        } else {
+            const int d = st * kSpBK + c.dr0 + 2 * i;
+            offA = d < c.D && c.wA ? c.oA[i] + (uint32_t)st * c.sA : 0xFFFFFF00u;
+            offB = d < c.D && c.wB ? c.oB[i] + (uint32_t)st * c.sB : 0xFFFFFF00u;
+        }
         // lanes past the block's 2 TW floats write nothing (EXEC), so the
         // next block is not overwritten
         if constexpr (!(MODE & kModeNoLoads)) {
@@ -100,28 +117,64 @@ __device__ __forceinline__ void split_body(const SpCtx &c, const BuildArgs &a, c
 #pragma unroll
         for (int y0 = 0; y0 < 4; ++y0) acc[x0][y0] = f32x4{0.f, 0.f, 0.f, 0.f};
     constexpr int KA = G::KA;
+    constexpr bool R3 = SL == 3;                          // the three-slot ring: refill in mid-step
     const int nks = (c.nst + 1) >> 1;                     // K steps (the launcher pads nst to even)
-    // stages of K steps 0 .. KA - 1 in flight
+    // stages of K steps 0 .. KA - 1 in flight (three slots: stages 0 - 2)
 #pragma unroll
-    for (int st = 0; st < 2 * KA; ++st)
-        if (st < c.nst) sp_issue<MODE, TW, SL>(c, smem, st);
+    for (int st = 0; st < G::Pro; ++st)
+        if (st < c.nst) sp_issue<MODE, TW, SL>(c, smem, st, st % SL);
+    int s0 = 0;                                           // three slots: the slot of stage 2 ks (wave-uniform)
     for (int ks = 0; ks < nks; ++ks) {
-        // RAW: my 8 DMA instructions of K step ks landed (the K steps issued
-        // after it may still fly: KA - 1 of them at ks = 0, from the
-        // prologue, KA - 2 later, since K step ks + KA - 1 is issued after
-        // this wait); WAR: my LDS reads of K step ks - 1 are done.  Barrier.
-        const int later = min(ks == 0 ? KA - 1 : KA - 2, nks - 1 - ks);
-        if (KA >= 3 && later >= 2) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory");
-        else if (later >= 1) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        if constexpr (R3) {
+            // RAW: my DMA instructions of stages 2 ks and 2 ks + 1 landed.
+            // They were issued in stage order, 4 per stage, and the only
+            // stage issued after them is 2 ks + 2 (prologue, or the mid-step
+            // refill of K step ks - 1) where it exists: nst is even, so that
+            // is every K step but the last.  Barrier.
+            if (ks + 1 < nks) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        } else {
+            // RAW: my 8 DMA instructions of K step ks landed (the K steps issued
+            // after it may still fly: KA - 1 of them at ks = 0, from the
+            // prologue, KA - 2 later, since K step ks + KA - 1 is issued after
+            // this wait); WAR: my LDS reads of K step ks - 1 are done.  Barrier.
+            const int later = min(ks == 0 ? KA - 1 : KA - 2, nks - 1 - ks);
+            if (KA >= 3 && later >= 2) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory");
+            else if (later >= 1) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        }
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        if (ks >= 1 && 2 * (ks + KA - 1) < c.nst) {      // K step ks + KA - 1 into the slots of K step ks - 1
-            sp_issue<MODE, TW, SL>(c, smem, 2 * (ks + KA - 1));
-            sp_issue<MODE, TW, SL>(c, smem, 2 * (ks + KA - 1) + 1);
+        if constexpr (!R3) {
+            if (ks >= 1 && 2 * (ks + KA - 1) < c.nst) {  // K step ks + KA - 1 into the slots of K step ks - 1
+                sp_issue<MODE, TW, SL>(c, smem, 2 * (ks + KA - 1), (2 * (ks + KA - 1)) % SL);
+                sp_issue<MODE, TW, SL>(c, smem, 2 * (ks + KA - 1) + 1, (2 * (ks + KA - 1) + 1) % SL);
+            }
         }
+        // Three slots: K step ks reads slots s0 and s0 + 1 (mod 3); the third
+        // holds stage 2 ks + 2.  Once EVERY wave has its last fragment of the
+        // step in registers (WAR: second barrier, run by every wave exactly
+        // once per K step whatever its FA / FB -- the waves without columns
+        // and kModeNoMath run it too), both slots are refilled: stage
+        // 2 ks + 3 (the next step's second half, the tail of this step to
+        // land) into s0 and stage 2 ks + 4 into s0 + 1.
+        auto mid = [&]() {
+            if constexpr (R3) {
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+                const int s1 = s0 == 2 ? 0 : s0 + 1;
+                if (2 * ks + 3 < c.nst) sp_issue<MODE, TW, SL>(c, smem, 2 * ks + 3, s0);
+                if (2 * ks + 4 < c.nst) sp_issue<MODE, TW, SL>(c, smem, 2 * ks + 4, s1);
+                s0 = s0 == 0 ? 2 : s0 - 1;                // (s0 + 2) mod 3: stage 2 (ks + 1)
+            }
+        };
         if constexpr (FA > 0 && !(MODE & kModeNoMath)) {
-            const char *st = smem + ((2 * ks + (g >> 1)) % SL) * G::Slot + lrow;
+            int slot = (2 * ks + (g >> 1)) % SL;
+            if constexpr (R3) {
+                slot = (g >> 1) ? (s0 == 2 ? 0 : s0 + 1) : s0;   // a select between two scalars
+            }
+            const char *st = smem + slot * G::Slot + lrow;
             const char *pb = st + 4 * (c.o1 + i);                        // F1 (B): this wave's w1
             const char *pa = st + G::Op + 4 * (c.o2 + i);                // F2 (A): this wave's w2
             auto mma6 = [&](f32x4 &c, const SplitFrag &x, const SplitFrag &y) {
@@ -144,6 +197,7 @@ __device__ __forceinline__ void split_body(const SpCtx &c, const BuildArgs &a, c
                 SplitFrag fa[FA];
 #pragma unroll
                 for (int m = 0; m < FA; ++m) fa[m] = sp_read<MODE, TW>(pa + 64 * m);
+                mid();
                 __builtin_amdgcn_sched_barrier(0);
                 __builtin_amdgcn_s_setprio(3);
 #pragma unroll
@@ -155,7 +209,12 @@ __device__ __forceinline__ void split_body(const SpCtx &c, const BuildArgs &a, c
             } else {
 #pragma unroll
                 for (int m = 0; m < FA; ++m) {
-                    const SplitFrag fa = sp_read<MODE, TW>(pa + 64 * m);
+                    // the last fragment: its raw dwords, the mid-step barrier
+                    // and refill (three slots), then its split
+                    float xa[8];
+                    sp_read_raw<TW>(pa + 64 * m, xa);
+                    if (m == FA - 1) mid();
+                    const SplitFrag fa = sp_split_raw<MODE>(xa);
                     if constexpr ((MODE & kModeMfmaPrio) != 0) {   // dev A/B: each fragment's MFMAs at raised priority
                         __builtin_amdgcn_sched_barrier(0);
                         __builtin_amdgcn_s_setprio(3);
@@ -168,23 +227,30 @@ __device__ __forceinline__ void split_body(const SpCtx &c, const BuildArgs &a, c
                     }
                 }
             }
+        } else {
+            mid();
         }
     }
     // the ring becomes the waves' epilogue staging images
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
+    // Three slots (168 VGPRs at most): the epilogue takes the lane number
+    // afresh, so that no register carries it through the K loop for it
+    int elane = lane;
+    if constexpr (R3)
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(elane));
     if constexpr (FA > 0 && (MODE & kModeSheared) != 0) {
         // RC_LAYOUT_DISPARITY: levels 0 and 2 written disparity-major
         const int w1e = c.M0 + c.o1 + 16 * FB;
-        epilogue_sheared<FA>(acc, a, row, c.M0 + c.o1, c.N0 + c.o2, lane,
+        epilogue_sheared<FA>(acc, a, row, c.M0 + c.o1, c.N0 + c.o2, elane,
                              lds_u32(smem + c.wave * G::Wave), w1e < a.W1 ? w1e : a.W1);
     } else if constexpr (FA > 0) {
         // the compile-time-geometry flushes (fp32 levels 0-2) unless the dev
         // A/B asks for the generic epilogue: config 2 262.5 vs 281.2 us
         // (profiles/r04/o/build_ablate.log, bit-identical)
         epilogue_swapped<FA, (MODE & kModeGenericEpi) ? MODE : (MODE | kModeFastEpi), NLM>(
-            acc, a, row, c.M0 + c.o1, c.N0 + c.o2, lane,
+            acc, a, row, c.M0 + c.o1, c.N0 + c.o2, elane,
             lds_u32(smem + c.wave * G::Wave), c.M0 + c.o1 + 16 * FB);
     }
 }
@@ -202,9 +268,10 @@ __device__ __forceinline__ void split_fb(int fb, const SpCtx &c, const BuildArgs
     else split_body<FA, 1, MODE, NLM, TW, SL>(c, a, smem, row);
 }
 
-// TW, SL: the ring geometry (SpRing); tiles at most TW wide (the launcher)
+// TW, SL: the ring geometry (SpRing); tiles at most TW wide (the launcher).
+// Three slots: 48.75 KB of LDS and at most 168 VGPRs, three workgroups per CU.
 template <int MODE, int NLM, int TW = 128, int SL = 4>
-__global__ __launch_bounds__(256, 2) void build_split_kernel(BuildArgs a, int nwg_total, int tf1, int tf2,
+__global__ __launch_bounds__(256, SL == 3 ? 3 : 2) void build_split_kernel(BuildArgs a, int nwg_total, int tf1, int tf2,
                                                              int tiles1, int tiles2) {
     __shared__ __attribute__((aligned(16))) char smem[SpRing<TW, SL>::Bytes];
     SpCtx c;
@@ -228,7 +295,8 @@ __global__ __launch_bounds__(256, 2) void build_split_kernel(BuildArgs a, int nw
     {
         // lane -> (row of its 2-row block, 4 columns); lanes >= TW / 2 idle
         const int w = 4 * (c.lane % (TW / 4));
-        c.dr0 = 4 * c.wave + (c.lane >= TW / 4 ? 1 : 0);
+        c.odd = c.lane >= TW / 4;
+        c.dr0 = 4 * c.wave + (c.odd ? 1 : 0);
         c.wA = w < c.tw1;
         c.wB = w < c.tw2;
 #pragma unroll
@@ -239,6 +307,8 @@ __global__ __launch_bounds__(256, 2) void build_split_kernel(BuildArgs a, int nw
         }
         c.sA = (uint32_t)kSpBK * (uint32_t)a.H * (uint32_t)a.W1 * 4u;
         c.sB = (uint32_t)kSpBK * (uint32_t)a.H * (uint32_t)a.W2 * 4u;
+        c.dA = 2u * (uint32_t)a.H * (uint32_t)a.W1 * 4u;
+        c.dB = 2u * (uint32_t)a.H * (uint32_t)a.W2 * 4u;
     }
     const long long img1 = (long long)a.D * a.H * a.W1, img2 = (long long)a.D * a.H * a.W2;
     c.r1 = make_rsrc(reinterpret_cast<const float *>(a.f1) + b * img1, clamp_bytes(img1 * 4));
@@ -256,6 +326,25 @@ __global__ __launch_bounds__(256, 2) void build_split_kernel(BuildArgs a, int nw
     else if (fa == 2) split_fb<2, MODE, NLM, TW, SL>(fb, c, a, smem, row);
     else if (fa == 1) split_fb<1, MODE, NLM, TW, SL>(fb, c, a, smem, row);
     else split_body<0, 1, MODE, NLM, TW, SL>(c, a, smem, row);
+}
+
+// Row-layout grids of more than one round at two workgroups per CU run the
+// three-slot ring at three per CU; a grid that two per CU hold at once (the
+// realtime shape) gains no residency from it and keeps the deeper prefetch of
+// four slots.  A HEURISTIC: measured at 480 (four slots
+// win), 4,320 and 17,856 workgroups (three win) on 256 CUs; nothing between
+// 513 and 4,320 was measured, and a grid of little more than one round may
+// sit on either side.  The CU count is that of the device current at the
+// first call, taken once: every GPU of a node this project runs on is the same.
+static bool sp_ring3(long long nwg) {
+    static const int ncu = [] {
+        int d = 0, n = 0;
+        if (hipGetDevice(&d) != hipSuccess ||
+            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n <= 0)
+            n = 256;
+        return n;
+    }();
+    return nwg > 2LL * ncu;
 }
 
 #ifdef RAFTCORR_DEV
@@ -302,10 +391,21 @@ hipError_t rc_launch_build_split(rc::BuildArgs &a, hipStream_t s) {
     }
     // up to 3 fused levels (the pair layout: 0 and 2 stored) keeps the
     // epilogue's level pointers out of the scalar registers
+    // (the four-slot launches come first in the source so that these kernels
+    // keep their places at the head of this file's code object, ahead of
+    // the three-slot ones)
+    if (!rc::sp_ring3(nwg)) {
+        if (a.nfused <= 3)
+            hipLaunchKernelGGL((rc::build_split_kernel<0, 3>), dim3((unsigned)nwg), dim3(256), 0, s, a, (int)nwg, tf1, tf2, tiles1, tiles2);
+        else
+            hipLaunchKernelGGL((rc::build_split_kernel<0, rc::kSpMaxFused>), dim3((unsigned)nwg), dim3(256), 0, s, a,
+                               (int)nwg, tf1, tf2, tiles1, tiles2);
+        return hipGetLastError();
+    }
     if (a.nfused <= 3)
-        hipLaunchKernelGGL((rc::build_split_kernel<0, 3>), dim3((unsigned)nwg), dim3(256), 0, s, a, (int)nwg, tf1, tf2, tiles1, tiles2);
+        hipLaunchKernelGGL((rc::build_split_kernel<0, 3, 128, 3>), dim3((unsigned)nwg), dim3(256), 0, s, a, (int)nwg, tf1, tf2, tiles1, tiles2);
     else
-        hipLaunchKernelGGL((rc::build_split_kernel<0, rc::kSpMaxFused>), dim3((unsigned)nwg), dim3(256), 0, s, a,
+        hipLaunchKernelGGL((rc::build_split_kernel<0, rc::kSpMaxFused, 128, 3>), dim3((unsigned)nwg), dim3(256), 0, s, a,
                            (int)nwg, tf1, tf2, tiles1, tiles2);
     return hipGetLastError();
 }

@@ -7,7 +7,8 @@ split-bf16 kernel (rc::build_split_kernel) under the dev library's
 RAFTCORR_SPLIT_MODE ablation flags: 0 product, 1 no operand loads, 2 no
 epilogue stores, 4 no MFMAs (sums combine; timing only, wrong values); a
 variant NAME=VALUE sets that dev knob instead (e.g. RAFTCORR_SPLIT_RING=85).
-Prints the median / min microseconds per launch of each variant.
+Prints the median / min microseconds per launch of each variant and the
+range of its per-round medians (the run-to-run spread inside this process).
 """
 import argparse
 import json
@@ -95,7 +96,13 @@ def main():
             os.environ.pop(k, None)
     ident = res.pop("bit_identical", {})
     nerr = res.pop("norm_err_vs_0", {})
-    out = {k: {"median_us": statistics.median(x), "min_us": min(x)} for k, x in res.items()}
+    # spread of the rounds: the medians of each round's --per launches
+    def rounds(x):
+        return [statistics.median(x[i:i + a.per]) for i in range(0, len(x), a.per)]
+    out = {k: {"median_us": statistics.median(x), "min_us": min(x),
+               "round_medians_min_us": min(rounds(x)), "round_medians_max_us": max(rounds(x)),
+               "round_medians_us": [round(r, 2) for r in rounds(x)]}
+           for k, x in res.items()}
     for k, v in ident.items():
         out[k]["bit_identical"] = v
         out[k]["norm_err_vs_mode0"] = nerr[k]
