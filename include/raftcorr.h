@@ -11,7 +11,10 @@
  *                   (model.py:297-316 and :267-281).
  *   rc_corr_lookup_conv  the lookup fused with BasicMotionEncoder.convc1 +
  *                   ReLU (model.py:199, :206), SURVEY.md §8f rank 1.
- *   rc_corr_lookup_chain  rc_corr_lookup for a pool-chain fp32 pyramid,
+ *   rc_corr_lookup_conv_backward  its gradient with respect to the
+ *                   correlation, the conv weight and the bias, for training
+ *                   with the fused layer (the lookup is recomputed).
+ *   rc_corr_lookup_chain rc_corr_lookup for a pool-chain fp32 pyramid,
  *                   reading levels 0-1 only (the default of CorrBlock1D).
  *   rc_corr_lookup_step  coords update + flow + lookup of one loop
  *                   iteration in one launch.
@@ -40,7 +43,7 @@
 extern "C" {
 #endif
 
-#define RC_ABI_VERSION 11
+#define RC_ABI_VERSION 12
 
 /* element types */
 #define RC_F32  0
@@ -194,6 +197,37 @@ int rc_corr_lookup_conv(const void *const *pyr, const int *widths, const long *p
                         long coord_batch_stride, int B, int H, int W1,
                         const float *weight, const float *bias, int cout, int relu,
                         float *out, void *stream);
+
+/* Backward of rc_corr_lookup_conv (ABI v12; autograd of model.py:199, :206
+ * taken together with the lookup), for training with the fused layer.  With
+ * corr and pre[c] = bias[c] + sum_k weight[c][k] * corr[k] recomputed from the
+ * pyramid exactly as the forward computes them (same helpers, same summation
+ * order, so the ReLU mask is the forward's bit for bit and nothing from the
+ * forward is kept), and g[c] = grad_out[b][c][h][w] * (relu ? pre[c] > 0 : 1):
+ *   grad_corr[b][k][h][w] = sum_c weight[c][k] * g[c]
+ *                        [B][levels*(2r+1)][H][W1] fp32 contiguous: the
+ *                        grad_out that rc_corr_lookup_backward and
+ *                        rc_corr_lookup_backward_calls consume;
+ *   grad_weight[c][k]   = sum over pixels of g[c] * corr[k],  [cout][levels*(2r+1)];
+ *   grad_bias[c]        = sum over pixels of g[c],            [cout].
+ *   All three are overwritten; each may be NULL and is then not computed (all
+ *   NULL: RC_EINVAL).  grad_out: [B][cout][H][W1] fp32 contiguous.  pyr ..
+ *   relu: rc_corr_lookup_conv's arguments, with its checks, flag refusals and
+ *   RC_EUNSUPPORTED cases (levels 2..4, radius 1..4; fp32 or bf16 pyramid).
+ *   workspace: RC_LOOKUP_CONV_BWD_WS(B*H*W1, cout, levels*(2r+1)) floats
+ *   holding one partial sum per workgroup of 256 pixels between the two
+ *   launches; required exactly when grad_weight or grad_bias is given (with
+ *   both NULL there is one launch).  B*H*W1 == 0 writes zeros to grad_weight
+ *   and grad_bias.  No atomics: every sum has a fixed order, so results repeat
+ *   bit for bit. */
+#define RC_LOOKUP_CONV_BWD_WS(P, cout, cin) \
+    ((((long long)(P) + 255) / 256) * (long long)(cout) * ((cin) + 1))   /* floats */
+int rc_corr_lookup_conv_backward(const void *const *pyr, const int *widths, const long *pyr_ld,
+                                 int pyr_dtype, int levels, int radius, const float *coords_x,
+                                 long coord_batch_stride, int B, int H, int W1,
+                                 const float *weight, const float *bias, int cout, int relu,
+                                 const float *grad_out, float *grad_corr, float *grad_weight,
+                                 float *grad_bias, float *workspace, void *stream);
 
 /* Lookup over a pool-chain fp32 pyramid (what rc_corr_build writes), same
  * arguments and bit-identical results as rc_corr_lookup with RC_F32, but

@@ -17,7 +17,7 @@ HEADER = os.path.join(os.path.dirname(_HERE), "include", "raftcorr.h")
 RC_F32, RC_BF16 = 0, 1
 RC_OK, RC_EINVAL, RC_EUNSUPPORTED, RC_EHIP = 0, 1, 2, 3
 RC_MAX_LEVELS = 8
-ABI_VERSION = 11
+ABI_VERSION = 12
 RC_SHADOW = 0xFF00  # pyr_dtype flags: every stored level carries a line-phase shadow copy
 RC_OUT_CHANNELS_LAST = 0x10000   # pyr_dtype flag: NHWC lookup output (pair kernel)
 RC_BUILD_EXACT_F32 = 0x20000     # rc_corr_build flag: exact fp32 MFMA kernel instead of the split-bf16 one
@@ -35,6 +35,11 @@ def rec_count(W2):
 def shear_rows(W2, W1, l):
     """RC_SHEAR_ROWS: rows (diagonals) per image row of disparity-major level l."""
     return (W2 >> l) + ((W1 - 1) >> l)
+
+
+def lookup_conv_bwd_ws(P, cout, cin):
+    """RC_LOOKUP_CONV_BWD_WS: workspace floats of rc_corr_lookup_conv_backward."""
+    return ((P + 255) // 256) * cout * (cin + 1)
 
 
 def shadow_level(l):
@@ -58,6 +63,9 @@ SIGNATURES = {
                             _i, _vp, _l, _i, _i, _i, _vp, _vp]),
     "rc_corr_lookup_conv": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_l), _i,
                                  _i, _i, _vp, _l, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "rc_corr_lookup_conv_backward": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_l), _i,
+                                          _i, _i, _vp, _l, _i, _i, _i, _vp, _vp, _i, _i,
+                                          _vp, _vp, _vp, _vp, _vp, _vp]),
     "rc_corr_lookup_chain": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_l), _i,
                                   _i, _i, _vp, _l, _i, _i, _i, _vp, _vp]),
     "rc_corr_lookup_step": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_l), _i,

@@ -33,7 +33,9 @@ RuntimeError (einsum, :324); coords that do not match the volume's
 RuntimeError (grid_sample dtype check, :275).
 
 Differences, all loud: tensors must live on a HIP device (no CPU fallback);
-the fused ``lookup_convc1`` is inference-only (asking for gradients raises);
+the fused ``lookup_convc1`` is inference-only unless called with
+``differentiable=True`` (asking for gradients raises otherwise), and
+``lookup_step`` is inference-only;
 bf16/fp16 fmaps are accepted (the reference crashes on them, SURVEY.md
 Appendix A D9; their gradients are computed in fp32): they, or
 an explicit ``pyramid_dtype=torch.bfloat16``, select the bf16 MFMA kernel and
@@ -42,6 +44,7 @@ a bf16 pyramid (bf16-level tolerance).
 import warnings
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 
@@ -265,6 +268,49 @@ def lookup_convc1(pyramid, coords, num_levels, radius, weight, bias=None, relu=T
             out.data_ptr(), _stream(coords.device))
     _lib.check(rc, "rc_corr_lookup_conv")
     return out
+
+
+def lookup_convc1_backward(pyramid, coords, num_levels, radius, weight, bias, relu, grad_out,
+                           need_corr=True, need_weight=True, need_bias=True):
+    """Run rc_corr_lookup_conv_backward: the gradients of ``lookup_convc1`` for
+    ``grad_out`` (B, cout, H, W1).  Returns ``(grad_corr, grad_weight,
+    grad_bias)``: (B, L(2r+1), H, W1), (cout, L(2r+1)) and (cout,) fp32, None
+    where not asked for.  The lookup is recomputed from ``pyramid``; grad_corr
+    is what ``lookup_backward`` / ``lookup_backward_calls`` take as grad_out."""
+    x, cbs = _check_coords(pyramid, coords)
+    B, _, H, W1 = coords.shape
+    cin = num_levels * (2 * radius + 1)
+    dev = coords.device
+    w = weight.detach().reshape(weight.shape[0], -1).float().contiguous()
+    if w.shape[1] != cin:
+        raise RuntimeError(f"lookup_convc1: weight has {w.shape[1]} input channels, lookup gives {cin}")
+    cout = w.shape[0]
+    b = bias.detach().float().contiguous() if bias is not None else None
+    if tuple(grad_out.shape) != (B, cout, H, W1):
+        raise RuntimeError(f"lookup_convc1: grad_out {tuple(grad_out.shape)} != {(B, cout, H, W1)}")
+    if not (need_corr or need_weight or need_bias):
+        return None, None, None
+    g = grad_out.detach().float().contiguous()
+    P = B * H * W1
+    gc = torch.empty((B, cin, H, W1), dtype=torch.float32, device=dev) if need_corr else None
+    gw = torch.empty((cout, cin), dtype=torch.float32, device=dev) if need_weight else None
+    gb = torch.empty((cout,), dtype=torch.float32, device=dev) if need_bias else None
+    if P == 0:
+        for t in (gw, gb):
+            if t is not None:
+                t.zero_()
+        return gc, gw, gb
+    # one partial sum per workgroup of 256 pixels, reduced by the second launch
+    ws = (torch.empty(_lib.lookup_conv_bwd_ws(P, cout, cin), dtype=torch.float32, device=dev)
+          if need_weight or need_bias else None)
+    keep, ptrs, widths, lds, dt = _level_args(pyramid, num_levels)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().rc_corr_lookup_conv_backward(
+            ptrs, widths, lds, dt, num_levels, radius, x.data_ptr(), cbs, B, H, W1,
+            w.data_ptr(), b.data_ptr() if b is not None else None, cout, int(relu), g.data_ptr(),
+            *(t.data_ptr() if t is not None else None for t in (gc, gw, gb, ws)), _stream(dev))
+    _lib.check(rc, "rc_corr_lookup_conv_backward")
+    return gc, gw, gb
 
 
 def lookup(pyramid, coords, num_levels, radius):
@@ -856,6 +902,39 @@ class _LookupFn(torch.autograd.Function):
         return ctx.state.token_grad(coords.device), None, None, None
 
 
+class _LookupConvFn(torch.autograd.Function):
+    """Autograd node of the differentiable fused lookup + convc1.  Saves
+    coords, weight and bias only: the backward recomputes the lookup
+    (rc_corr_lookup_conv_backward), so the correlation tensor is kept neither
+    by the forward nor for the backward.  Like _LookupFn it consumes the
+    block's token (None when the fmaps need no gradient) and hands its
+    grad_corr to the shared _GradState."""
+
+    @staticmethod
+    def forward(ctx, token, coords, weight, bias, state, levels, num_levels, radius, relu):
+        ctx.state = state if token is not None else None
+        ctx.levels, ctx.cfg = levels, (num_levels, radius, relu)
+        ctx.save_for_backward(coords, weight, bias)
+        return lookup_convc1(levels, coords, num_levels, radius, weight, bias, relu)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        coords, weight, bias = ctx.saved_tensors
+        num_levels, radius, relu = ctx.cfg
+        need_corr = ctx.state is not None
+        need_w = ctx.needs_input_grad[2]
+        need_b = bias is not None and ctx.needs_input_grad[3]
+        gc, gw, gb = lookup_convc1_backward(ctx.levels, coords, num_levels, radius, weight, bias, relu,
+                                            grad_out, need_corr, need_w, need_b)
+        token_grad = None
+        if need_corr:
+            ctx.state.accumulate(coords, gc)
+            token_grad = ctx.state.token_grad(coords.device)
+        return (token_grad, None, gw.view(weight.shape).to(weight.dtype) if need_w else None,
+                gb.view(bias.shape).to(bias.dtype) if need_b else None, None, None, None, None, None)
+
+
 class CorrBlock1D:
     """model.py:283-326, on the gfx950 kernels (see module docstring)."""
 
@@ -1166,18 +1245,30 @@ class CorrBlock1D:
             corr = corr.contiguous(memory_format=torch.channels_last)
         return corr, new, flow
 
-    def lookup_convc1(self, coords, weight, bias=None, relu=True):
+    def lookup_convc1(self, coords, weight, bias=None, relu=True, differentiable=False):
         """``relu(convc1(self(coords)))`` in one launch:
         the motion encoder's first layer (model.py:199, :206) fused into the
         lookup, so the (B, L(2r+1), H, W1) correlation never reaches HBM.
-        Inference only."""
-        if torch.is_grad_enabled() and (self._token is not None or weight.requires_grad):
+
+        ``differentiable=False`` is inference-only and raises when gradients
+        are being recorded.  ``differentiable=True`` records an autograd node
+        (first order only) when grad is enabled: its backward recomputes the
+        lookup (rc_corr_lookup_conv_backward), returns the
+        gradients of ``weight`` and ``bias`` and feeds the block's level
+        gradients like a plain ``self(coords)`` call, so the correlation
+        tensor is stored neither by the forward nor for the backward."""
+        grad = torch.is_grad_enabled()
+        if not differentiable and grad and (self._token is not None or weight.requires_grad):
             raise RuntimeError("CorrBlock1D.lookup_convc1 is inference-only; use "
-                               "convc1(block(coords)) when gradients are needed")
+                               "convc1(block(coords)) when gradients are needed, or pass "
+                               "differentiable=True")
         if self._sheared is not None or self._records is not None:
             raise RuntimeError(f"CorrBlock1D.lookup_convc1: not available with layout={self.layout!r}")
-        return lookup_convc1(self._read_levels(), coords, self.num_levels, self.radius, weight,
-                             bias, relu)
+        levels = self._read_levels()
+        if differentiable and grad:
+            return _LookupConvFn.apply(self._token, coords.detach(), weight, bias, self._state, levels,
+                                       self.num_levels, self.radius, bool(relu))
+        return lookup_convc1(levels, coords, self.num_levels, self.radius, weight, bias, relu)
 
     @staticmethod
     def corr(fmap1, fmap2, exact_f32=False):

@@ -675,6 +675,47 @@ extern "C" int rc_corr_lookup_conv(const void *const *pyr, const int *widths, co
                   "rc_corr_lookup_conv: launch");
 }
 
+extern "C" int rc_corr_lookup_conv_backward(const void *const *pyr, const int *widths, const long *pyr_ld,
+                                            int pyr_dtype, int levels, int radius, const float *coords_x,
+                                            long coord_batch_stride, int B, int H, int W1,
+                                            const float *weight, const float *bias, int cout, int relu,
+                                            const float *grad_out, float *grad_corr, float *grad_weight,
+                                            float *grad_bias, float *workspace, void *stream) {
+    g_err[0] = 0;
+    const char *who = "rc_corr_lookup_conv_backward";
+    rc::LookupArgs a;
+    bool empty;
+    if (int e = check_flags(who, pyr_dtype, false)) return e;
+    int rc = prep_lookup(who, pyr, widths, pyr_ld, pyr_dtype, levels, radius, coords_x,
+                         coord_batch_stride, B, H, W1, grad_out, a, &empty);
+    if (rc) return rc;
+    pyr_dtype &= 0xFF;
+    if (levels < 2 || levels > 4 || radius > 4)
+        return fail(RC_EUNSUPPORTED, "%s: levels 2..4 and radius 1..4 only", who);
+    if (cout < 1 || cout > (1 << 20)) return fail(RC_EINVAL, "%s: cout=%d", who, cout);
+    if (!grad_corr && !grad_weight && !grad_bias)
+        return fail(RC_EINVAL, "%s: none of grad_corr, grad_weight, grad_bias requested", who);
+    const bool sums = grad_weight || grad_bias;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (empty) {   // sums over no pixels
+        const size_t cin = (size_t)levels * (2 * radius + 1);
+        if (grad_weight)
+            if (hipError_t e = hipMemsetAsync(grad_weight, 0, (size_t)cout * cin * sizeof(float), s))
+                return hip_rc(e, "rc_corr_lookup_conv_backward: memset");
+        if (grad_bias)
+            if (hipError_t e = hipMemsetAsync(grad_bias, 0, (size_t)cout * sizeof(float), s))
+                return hip_rc(e, "rc_corr_lookup_conv_backward: memset");
+        return RC_OK;
+    }
+    if (!weight) return fail(RC_EINVAL, "%s: null weight", who);
+    if (sums && !workspace)
+        return fail(RC_EINVAL, "%s: grad_weight / grad_bias need a workspace of "
+                    "RC_LOOKUP_CONV_BWD_WS(P, cout, cin) floats", who);
+    return hip_rc(rc_launch_lookup_conv_bwd(a, radius, pyr_dtype == RC_BF16, weight, bias, cout, relu,
+                                            grad_out, grad_corr, grad_weight, grad_bias, workspace, s),
+                  "rc_corr_lookup_conv_backward: launch");
+}
+
 extern "C" int rc_convex_upsample(const float *flow, const float *mask, int N, int C, int H, int W,
                                   int factor, float *out, void *stream) {
     g_err[0] = 0;

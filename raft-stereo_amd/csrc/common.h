@@ -233,6 +233,12 @@ hipError_t rc_launch_pool(const void *in, long long ld_in, void *out, long long 
 hipError_t rc_launch_lookup(const rc::LookupArgs &a, int radius, int pyr_bf16, hipStream_t s);
 hipError_t rc_launch_lookup_conv(const rc::LookupArgs &a, int radius, int pyr_bf16, const float *w,
                                  const float *b, int cout, int relu, float *out, hipStream_t s);
+// grad_corr / grad_weight / grad_bias may be null (not computed); workspace is
+// used only when grad_weight or grad_bias is given
+hipError_t rc_launch_lookup_conv_bwd(const rc::LookupArgs &a, int radius, int pyr_bf16, const float *w,
+                                     const float *b, int cout, int relu, const float *grad_out,
+                                     float *grad_corr, float *grad_weight, float *grad_bias,
+                                     float *workspace, hipStream_t s);
 hipError_t rc_launch_lookup_chain(const rc::LookupArgs &a, int radius, hipStream_t s);
 hipError_t rc_launch_lookup_pair(const rc::LookupArgs &a, int radius, int pyr_bf16, hipStream_t s);
 hipError_t rc_launch_lookup_bwd(const rc::LookupBwdArgs &a, int radius, hipStream_t s);

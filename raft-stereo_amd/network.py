@@ -304,7 +304,9 @@ class RAFTStereo(nn.Module):
                     predictions.append(flow)
             else:
                 if fused:                               # lookup + convc1 + ReLU, one launch
-                    corr = corr_fn.lookup_convc1(coords1, enc.convc1.weight, enc.convc1.bias)
+                    # with grad enabled it carries rc_corr_lookup_conv_backward
+                    corr = corr_fn.lookup_convc1(coords1, enc.convc1.weight, enc.convc1.bias,
+                                                 differentiable=torch.is_grad_enabled())
                 else:
                     corr = corr_fn(coords1)             # the hot path, every iteration
                 flow = coords1 - coords0
