@@ -85,6 +85,23 @@ template <int VW>
 __device__ __forceinline__ void store_rows16(uint32_t st, int p, int cw, void *lvl, long long ld,
                                              bool bf16, long long rowbase, int w1_0, int col0, int W1,
                                              int Wl, int lane, long long sh) {
+    if constexpr (VW == 1) {
+        // an image wider than the wave (the bf16 ring's 80-column wave tiles
+        // with a row stride or first column that allows only scalar stores):
+        // 64 / lpr below would be 0 rows per instruction and the loop would
+        // never advance -- one row at a time, 64 columns per pass
+        if (cw > 64) {
+            for (int R = 0; R < 16; ++R) {
+                const int w1 = w1_0 + R;
+                for (int j = lane; j < cw; j += 64) {
+                    float x0;
+                    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(x0) : "v"(st + 4 * (R * p + j)));
+                    if (w1 < W1 && col0 + j < Wl) store_vec<1>(lvl, bf16, (rowbase + w1) * ld + col0 + j, &x0, sh);
+                }
+            }
+            return;
+        }
+    }
     const int lpr = cw / VW;                 // lanes per row
     const int rpi = 64 / lpr;                // rows per instruction
     const int Rl = lane / lpr, j = (lane - Rl * lpr) * VW;

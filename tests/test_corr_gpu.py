@@ -301,9 +301,9 @@ BF16_SHAPES = [
     (2, 256, 2, 311, 311, 4, 4),    # config-3 width: rows not 16-B aligned
     (1, 96, 3, 40, 57, 3, 3),       # D % 32 != 0, odd W2
     (1, 37, 2, 24, 33, 4, 2),
-    # bf16-fmap ring kernel: 4 waves along w2 x 3 w2 tiles, 6 w1 tiles
+    # bf16-fmap ring kernel: 3 waves along w2 x 5 fragments (240-wide tiles), 3 w2 tiles, 6 w1 tiles
     (1, 64, 2, 700, 720, 4, 4),
-    (1, 256, 1, 150, 130, 3, 4),    # 3 waves along w2; idle waves in the last w1 tile
+    (1, 256, 1, 150, 130, 3, 4),    # 2 waves along w2 x 5 fragments; idle waves in the last w1 tile
     (1, 40, 2, 100, 100, 4, 2),     # 2 waves along w2, D % 32 != 0
 ]
 
