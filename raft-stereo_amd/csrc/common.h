@@ -116,7 +116,7 @@ struct BuildArgs {
     float sq;                 // sqrtf(D)
     int pow2;                 // sqrt(D) is a power of two -> multiply is exact
     int pyr_bf16;             // store pyramid as bf16
-    int stagger;              // dev-only: first-round stagger unit (s_sleep(127) count)
+    int stagger;              // reserved (no reader): keeps the kernarg offsets of the fields below
     // line-phase shadow copies (ABI v5, RC_SHADOW): a stored level l is also
     // written at (char*)lvl[l] + shadow[l] bytes (0 = no copy)
     long long shadow[kMaxLevels];
@@ -221,12 +221,24 @@ struct BuildBwdArgs {
     int dev_only;                   // dev library timing probe: 1 = dF1 tiles only, 2 = dF2 only
 };
 
+// CUs of the device current at the first call, taken once: every GPU of a
+// node this project runs on is the same.  256 when the query fails.
+inline int device_cus() {
+    static const int ncu = [] {
+        int d = 0, n = 0;
+        if (hipGetDevice(&d) != hipSuccess ||
+            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n <= 0)
+            n = 256;
+        return n;
+    }();
+    return ncu;
+}
+
 }  // namespace rc
 
 // Host-side launchers (defined in the .hip files, called by capi.cpp).
 hipError_t rc_launch_build_f32(const rc::BuildArgs &a, hipStream_t s);
 hipError_t rc_launch_build_split(rc::BuildArgs &a, hipStream_t s);     // may lower a.nfused
-hipError_t rc_launch_build_planes(rc::BuildArgs &a, hipStream_t s);   // dev library only
 hipError_t rc_launch_build_bf16mma(rc::BuildArgs &a, int in_bf16, hipStream_t s);   // may lower a.nfused
 hipError_t rc_launch_pool(const void *in, long long ld_in, void *out, long long ld_out, long rows,
                           int W_in, int bf16, hipStream_t s);

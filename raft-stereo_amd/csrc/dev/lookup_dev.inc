@@ -78,20 +78,12 @@ static hipError_t dev_launch_conv(const LookupArgs &a, int bf16, const float *w,
 // chunk loads, the pre-COOP kernel); 4 the whole records fetched
 // cooperatively into LDS (COOP: the product since r06o), 5 / 6 COOP without
 // output stores / loads only, 7 / 8 COOP / per-lane loads capped at 4 waves
-// per SIMD (128 VGPRs: 5 / 3 spilled), 9 per-lane loads (the pre-COOP product),
-// 10 two groups per wave (lookup_records2_kernel, channels-last), 11 the same
-// with NCHW stores into the channels-last buffer (timing only).
+// per SIMD (128 VGPRs: 5 / 3 spilled), 9 per-lane loads (the pre-COOP product).
 template <int R>
 static hipError_t dev_launch_records(const LookupArgs &a, hipStream_t s) {
     const int v = dev_knob("RAFTCORR_REC_LOOKUP");
-    if (v < 1 || v > 11 || !a.out_cl) return hipErrorNotSupported;
+    if (v < 1 || v > 9 || !a.out_cl) return hipErrorNotSupported;
     const unsigned nblk = (unsigned)((a.P + 255) / 256);
-    if (v >= 10) {   // two groups per wave (lookup_records2_kernel)
-        const unsigned nb2 = (unsigned)((a.P + 511) / 512);
-        if (v == 10) hipLaunchKernelGGL((lookup_records2_kernel<R, true>), dim3(nb2), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((lookup_records2_kernel<R, false>), dim3(nb2), dim3(256), 0, s, a);
-        return hipGetLastError();
-    }
     if (v == 1) hipLaunchKernelGGL((lookup_records_kernel<R, true, 1>), dim3(nblk), dim3(256), 0, s, a);
     else if (v == 2) hipLaunchKernelGGL((lookup_records_kernel<R, true, 2>), dim3(nblk), dim3(256), 0, s, a);
     else if (v == 3) hipLaunchKernelGGL((lookup_records_kernel<R, true, 3>), dim3(nblk), dim3(256), 0, s, a);

@@ -1,15 +1,7 @@
 // Dev-library part of volume.hip (libraftcorr_dev.so only; included inside
 // namespace rc after the product kernels).  RAFTCORR_BUILD_MODE selects
-// ablation modes and measured-and-not-kept variants; every dev_launch_*
-// returns hipErrorNotSupported (or false) when the knob asks for none.
-
-// dev: the 6-wave shape (128-wide w2 tiles, 75 / 65 KB of LDS) resident
-// twice per CU, so two independent barrier chains share each CU
-template <int MODE>
-static void launch_bf16_ring_two(const BuildArgs &a, bool defer, int per_cu, hipStream_t s) {
-    if (defer) launch_bf16_ring_n<2, 4, 4, MODE, true>(a, s, per_cu);
-    else launch_bf16_ring_n<2, 4, 3, MODE, false>(a, s, per_cu);
-}
+// ablation modes; every dev_launch_* returns hipErrorNotSupported (or false)
+// when the knob asks for none.
 
 // per-wave bf16 kernel: 1 no operand loads, 2 no stores, 3 neither
 template <bool IN_BF16, bool ALIGNED>
@@ -27,20 +19,13 @@ static bool dev_launch_bf16_pw(const BuildArgs &a, unsigned nwg, hipStream_t s) 
 // stores, 41 no DMA, 44 no fragment reads / MFMA, 45 neither, 42 / 43 MFMA
 // without fragment reads (and no DMA), 46 no DMA with stores, 47 no DMA no
 // MFMA with stores, 54 47 into L2-resident rows, 55 the product into
-// L2-resident rows; 49 / 50 the 6-wave shape 2 / 1 per CU, 51 the same
-// without stores; 52 / 53 deferred stores spread over 8 stages / staggered
-// by wave parity.
+// L2-resident rows.
 static hipError_t dev_launch_bf16mma(BuildArgs &a, B16Shape &sh, hipStream_t s) {
     const int mode = dev_knob("RAFTCORR_BUILD_MODE");
     if (mode == 32) sh = B16Shape{0, 0, false};
-    if (!sh.nwn || mode < 40 || mode > 55) return hipErrorNotSupported;
+    if (!sh.nwn || mode < 40 || mode > 55 || (mode >= 49 && mode <= 53)) return hipErrorNotSupported;
     if (a.nfused > kB16MaxFused) a.nfused = kB16MaxFused;
     switch (mode) {
-        case 52: launch_bf16_ring<kModeSpread>(a, sh, s); break;
-        case 53: launch_bf16_ring<kModeStagger>(a, sh, s); break;
-        case 49: launch_bf16_ring_two<0>(a, sh.defer, 2, s); break;
-        case 50: launch_bf16_ring_two<0>(a, sh.defer, 1, s); break;
-        case 51: launch_bf16_ring_two<2>(a, sh.defer, 2, s); break;
         case 40: launch_bf16_ring<2>(a, sh, s); break;
         case 41: launch_bf16_ring<3>(a, sh, s); break;
         case 44: launch_bf16_ring<6>(a, sh, s); break;
@@ -59,27 +44,22 @@ static hipError_t dev_launch_bf16mma(BuildArgs &a, B16Shape &sh, hipStream_t s) 
 // record build (RC_LAYOUT_RECORDS), RAFTCORR_REC_MODE (timing only, wrong
 // records except 0): 1 records gathered but not stored, 2 stored into 8
 // L2-resident image rows, 3 no gather (piece images only), 4 no piece images
-// and no gather (the K loop, the LDS footprint and the held registers only),
-// 5 the loader waves gather and store (the compute waves write the images),
-// 6 non-temporal record stores
+// and no gather (the K loop, the LDS footprint and the held registers only)
 static hipError_t dev_launch_records(const BuildArgs &a, int nwn, hipStream_t s) {
     const int mode = dev_knob("RAFTCORR_REC_MODE");
-    if (mode < 1 || mode > 6 || nwn != 5) return hipErrorNotSupported;
+    if (mode < 1 || mode > 4 || nwn != 5) return hipErrorNotSupported;
     constexpr int R = kModeRecords;
     switch (mode) {
         case 1: launch_bf16_ring_n<5, 4, 4, R | kModeRecNoStore, true>(a, s); break;
         case 2: launch_bf16_ring_n<5, 4, 4, R | kModeL2Stores, true>(a, s); break;
         case 3: launch_bf16_ring_n<5, 4, 4, R | kModeRecNoEmit, true>(a, s); break;
-        case 5: launch_bf16_ring_n<5, 4, 4, R | kModeRecLoaderEmit, true>(a, s); break;
-        case 6: launch_bf16_ring_n<5, 4, 4, R | kModeRecNT, true>(a, s); break;
         default: launch_bf16_ring_n<5, 4, 4, R | kModeNoStores, true>(a, s); break;
     }
     return hipGetLastError();
 }
 
 // exact fp32 build: 2 ring without epilogue stores, 4 / 5 a 4- / 5-slot
-// ring; 128 + flags the direct-load kernel (1 no operand loads, 2 no stores,
-// 64 stagger)
+// ring; 128 + flags the direct-load kernel (1 no operand loads, 2 no stores)
 static hipError_t dev_launch_f32(const BuildArgs &a, unsigned n, hipStream_t s) {
     switch (dev_knob("RAFTCORR_BUILD_MODE")) {
         case 2: launch_ring<2>(a, s); break;
@@ -89,7 +69,6 @@ static hipError_t dev_launch_f32(const BuildArgs &a, unsigned n, hipStream_t s) 
         case 129: launch<true, 2, 1>(a, n, s); break;
         case 130: launch<true, 2, 2>(a, n, s); break;
         case 131: launch<true, 2, 3>(a, n, s); break;
-        case 192: launch<true, 2, 64>(a, n, s); break;
         default: return hipErrorNotSupported;
     }
     return hipGetLastError();

@@ -12,12 +12,9 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 // Dev-only ablation flags (RAFTCORR_BUILD_MODE): 1 = no operand loads,
 // 2 = no epilogue stores.  Product launches use 0.
 enum { kModeNoLoads = 1, kModeNoStores = 2, kModeNoMath = 4, kModeAlignedSrc = 8, kModeNoFragReads = 16,
-       kModeStagger = 64, kModeNoMfma = 512, kModeNoSplit = 1024, kModeSpread = 2048, kModeSheared = 4096,
-       kModePackedSub = 8192,
-       kModeL2Stores = 65536, kModeDirect = 131072, kModeFastEpi = 262144, kModeGenericEpi = 524288,
-       kModePairEpi = 1048576, kModeRecords = 1 << 23, kModeRecNoStore = 1 << 24, kModeRecNoEmit = 1 << 25,
-       kModeRecLoaderEmit = 1 << 26, kModeRecNT = 1 << 27,
-       kModePhasePrio = 1 << 28, kModeMfmaPrio = 1 << 29 };
+       kModeNoMfma = 512, kModeNoSplit = 1024, kModeSheared = 4096,
+       kModeL2Stores = 65536, kModeFastEpi = 262144,
+       kModeRecords = 1 << 23, kModeRecNoStore = 1 << 24, kModeRecNoEmit = 1 << 25 };
 
 // VW consecutive level values -> memory (fp32, or bf16 rounded to nearest even).
 template <int VW>
@@ -206,49 +203,6 @@ __device__ __forceinline__ void flush_rows16_fast(uint32_t st, const BuildArgs &
     }
 }
 
-// The same flush split in two, so that several images' reads share one
-// wait: flush_issue (LDS reads of rows [0, 16) of a staged image) and
-// flush_store (their stores), with flush_settle between them.
-template <int CW, int L>
-struct FlushRegs {
-    static constexpr int LP = CW / 4, RPI = 64 / LP, NI = (16 + RPI - 1) / RPI;
-    f32x4 x[NI];
-};
-template <int CW, int L>
-__device__ __forceinline__ void flush_issue(FlushRegs<CW, L> &f, uint32_t st, int lane) {
-    typedef FlushRegs<CW, L> F;
-    const int Rl = lane / F::LP, j = (lane - Rl * F::LP) * 4;
-#pragma unroll
-    for (int k = 0; k < F::NI; ++k) {
-        const int R = k * F::RPI + Rl;
-        const uint32_t src = st + 4 * ((R < 16 ? R : 15) * (CW + 4) + j);
-        asm volatile("ds_read_b128 %0, %1" : "=v"(f.x[k]) : "v"(src));
-    }
-}
-// after the shared wait: the registers pass through an asm that follows it,
-// so no use of them moves above the wait
-template <int CW, int L>
-__device__ __forceinline__ void flush_settle(FlushRegs<CW, L> &f) {
-#pragma unroll
-    for (int k = 0; k < FlushRegs<CW, L>::NI; ++k) asm volatile("" : "+v"(f.x[k]));
-}
-template <int CW, int L>
-__device__ __forceinline__ void flush_store(const FlushRegs<CW, L> &f, const BuildArgs &a, long long rowbase,
-                                            int w1_0, int n0, int w1e, int lane) {
-    typedef FlushRegs<CW, L> F;
-    const int Rl = lane / F::LP, j = (lane - Rl * F::LP) * 4;
-    const int col = (n0 >> L) + j;
-    const bool lok = Rl < F::RPI && col < (a.W2 >> L);
-#pragma unroll
-    for (int k = 0; k < F::NI; ++k) {
-        const int R = k * F::RPI + Rl, w1 = w1_0 + R;
-        if (lok && R < 16 && w1 < w1e) {
-            const float v[4] = {f.x[k][0], f.x[k][1], f.x[k][2], f.x[k][3]};
-            store_vec<4>(a.lvl[L], false, (rowbase + w1) * a.ld[L] + col, v, a.shadow[L]);
-        }
-    }
-}
-
 // Disparity-major stores (RC_LAYOUT_DISPARITY, ABI v9) of the pair layout's
 // levels 0 and 2: level i of row block `row` is S_i[k][w1] with
 // k = (w1 >> i) - j + (W2 >> i) - 1, row stride a.ld[i], a.shk[i] rows per
@@ -384,79 +338,12 @@ __device__ __forceinline__ void epilogue_swapped(f32x4 (&acc)[FMA][4], const Bui
     // one of 8 rows, so the same instructions write L2-resident lines
     const long long rowbase = (long long)((MODE & kModeL2Stores) ? (row & 7) : row) * a.W1;
     const int nl = a.nfused < NLM ? a.nfused : NLM;
-    if constexpr ((MODE & kModeFastEpi) != 0 && (MODE & (kModeNoStores | kModeL2Stores | kModeDirect)) == 0) {
+    if constexpr ((MODE & kModeFastEpi) != 0 && (MODE & (kModeNoStores | kModeL2Stores)) == 0) {
         // fp32 levels 0-2, power-of-two scale, 16-B aligned rows: the
         // geometry of every flush is compile-time (flush_rows16_fast)
         const bool fast = !bf && a.pow2 && (!a.lvl[0] || a.ld[0] % 4 == 0) &&
                           (nl < 2 || !a.lvl[1] || a.ld[1] % 4 == 0) && (nl < 3 || !a.lvl[2] || a.ld[2] % 4 == 0) &&
                           (nl < 4 || !a.lvl[3] || a.ld[3] % 2 == 0);
-        if constexpr (NLM <= 3 && (MODE & kModePairEpi) != 0) {
-            if (fast) {
-                // two fragment columns at a time: every level image of both
-                // staged in its own region of the wave's 16 KB of the ring,
-                // all their reads, ONE wait, then all their stores
-                const int g = lane0 >> 4, i = lane0 & 15;
-                constexpr int S0 = 16 * (WT + 4) * 4, S1 = 16 * (WT / 2 + 4) * 4, S2 = 16 * (WT / 4 + 4) * 4;
-                constexpr int SNB = S0 + S1 + S2;
-#pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    FlushRegs<WT, 0> r0[2];
-                    FlushRegs<WT / 2, 1> r1[2];
-                    FlushRegs<WT / 4, 2> r2[2];
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const int nb = 2 * p + k;
-                        const uint32_t b = st0 + k * SNB;
-                        float v[FMA][4];
-#pragma unroll
-                        for (int ma = 0; ma < FMA; ++ma)
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) v[ma][r] = acc[ma][nb][r] * a.scale;
-                        if (a.lvl[0]) {
-#pragma unroll
-                            for (int ma = 0; ma < FMA; ++ma)
-                                lds_st4(b + 4 * (i * (WT + 4) + 16 * ma + 4 * g), f32x4{v[ma][0], v[ma][1], v[ma][2], v[ma][3]});
-                            flush_issue(r0[k], b, lane0);
-                        }
-                        if (nl < 2) continue;
-                        float u[FMA][2];
-#pragma unroll
-                        for (int ma = 0; ma < FMA; ++ma) {
-                            u[ma][0] = pool2(v[ma][0], v[ma][1], false);
-                            u[ma][1] = pool2(v[ma][2], v[ma][3], false);
-                        }
-                        if (a.lvl[1]) {
-#pragma unroll
-                            for (int ma = 0; ma < FMA; ++ma)
-                                lds_st2(b + S0 + 4 * (i * (WT / 2 + 4) + 8 * ma + 2 * g), f32x2{u[ma][0], u[ma][1]});
-                            flush_issue(r1[k], b + S0, lane0);
-                        }
-                        if (nl < 3) continue;
-                        if (a.lvl[2]) {
-#pragma unroll
-                            for (int ma = 0; ma < FMA; ++ma)
-                                lds_st1(b + S0 + S1 + 4 * (i * (WT / 4 + 4) + 4 * ma + g), pool2(u[ma][0], u[ma][1], false));
-                            flush_issue(r2[k], b + S0 + S1, lane0);
-                        }
-                    }
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        flush_settle(r0[k]);
-                        flush_settle(r1[k]);
-                        flush_settle(r2[k]);
-                    }
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const int w1_0 = m0 + 16 * (2 * p + k);
-                        if (a.lvl[0]) flush_store(r0[k], a, rowbase, w1_0, n0, w1e, lane0);
-                        if (nl >= 2 && a.lvl[1]) flush_store(r1[k], a, rowbase, w1_0, n0, w1e, lane0);
-                        if (nl >= 3 && a.lvl[2]) flush_store(r2[k], a, rowbase, w1_0, n0, w1e, lane0);
-                    }
-                }
-                return;
-            }
-        }
         if (fast) {
             const int g = lane0 >> 4, i = lane0 & 15;
 #pragma unroll
@@ -532,57 +419,6 @@ __device__ __forceinline__ void epilogue_swapped(f32x4 (&acc)[FMA][4], const Bui
             }
             return;
         }
-    }
-    if constexpr ((MODE & kModeDirect) != 0) {
-        // each lane stores its own values straight from the registers (no
-        // LDS image): level l of lane (i, g) for fragment (ma, nb) is row
-        // w1 = m0 + 16nb + i, columns ((n0 + 16ma + 4g) >> l) .. +(4 >> l)
-        const int g = lane0 >> 4, i = lane0 & 15;
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) {
-            const int w1 = m0 + 16 * nb + i;
-            const bool rok = w1 < w1e;
-            const long long rb = rowbase + w1;
-            float v[FMA][4];
-#pragma unroll
-            for (int ma = 0; ma < FMA; ++ma)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float x = acc[ma][nb][r];
-                    const float c = a.pow2 ? x * a.scale : x / a.sq;
-                    v[ma][r] = bf ? round_bf16(c) : c;
-                }
-            auto put = [&](int l, int col, const float *x, int n) {   // n consecutive values of level l
-                if (!a.lvl[l] || !rok || col >= (a.W2 >> l)) return;
-                const long long e = rb * a.ld[l] + col;
-                if (n == 4 && a.ld[l] % 4 == 0) store_vec<4>(a.lvl[l], bf, e, x, a.shadow[l]);
-                else if (n >= 2 && a.ld[l] % 2 == 0) {
-                    store_vec<2>(a.lvl[l], bf, e, x, a.shadow[l]);
-                    if (n == 4) store_vec<2>(a.lvl[l], bf, e + 2, x + 2, a.shadow[l]);
-                } else {
-                    for (int k = 0; k < n; ++k) store_vec<1>(a.lvl[l], bf, e + k, x + k, a.shadow[l]);
-                }
-            };
-#pragma unroll
-            for (int ma = 0; ma < FMA; ++ma) {
-                put(0, n0 + 16 * ma + 4 * g, v[ma], 4);
-                if (nl < 2) continue;
-                const float u[2] = {pool2(v[ma][0], v[ma][1], bf), pool2(v[ma][2], v[ma][3], bf)};
-                put(1, (n0 >> 1) + 8 * ma + 2 * g, u, 2);
-                if (nl < 3) continue;
-                const float s2 = pool2(u[0], u[1], bf);
-                put(2, (n0 >> 2) + 4 * ma + g, &s2, 1);
-                if (nl < 4) continue;
-                const float o3 = __shfl_xor(s2, 16);
-                const float s3 = (g & 1) ? pool2(o3, s2, bf) : pool2(s2, o3, bf);
-                if (!(g & 1)) put(3, (n0 >> 3) + 2 * ma + (g >> 1), &s3, 1);
-                if (nl < 5) continue;
-                const float o4 = __shfl_xor(s3, 32);
-                const float s4 = (g & 2) ? pool2(o4, s3, bf) : pool2(s3, o4, bf);
-                if (g == 0) put(4, (n0 >> 4) + ma, &s4, 1);
-            }
-        }
-        return;
     }
     // one loop body for the four columns (code size, registers): column nb
     // is always acc[.][0], the others move down one per pass

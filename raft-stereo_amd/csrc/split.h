@@ -35,19 +35,16 @@ __device__ __forceinline__ float sp_sub(float a, float b) {
 
 // 8 consecutive d of one w -> head, middle and low bf16 pieces (each exact
 // residual of the previous: x = h + m + l for finite |x| < 3.39e38).
-// SCALAR (default): residuals by sp_sub (v_sub_f32); false: as the compiler
-// packs them (the dev A/B kModePackedSub; config 2 build 286 vs 280 us,
-// bit-identical, profiles/r04/d/build_ablate.log).
-template <bool SCALAR = true>
+// Residuals by sp_sub (v_sub_f32), not as the compiler packs them (config 2
+// build 286 vs 280 us, bit-identical, profiles/r04/d/build_ablate.log).
 __device__ __forceinline__ SplitFrag sp_split(const float (&x)[8]) {
     u32x4s h, m, l;
-    auto sub = [](float a, float b) { return SCALAR ? sp_sub(a, b) : a - b; };
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const uint32_t hp = sp_pack(x[2 * k], x[2 * k + 1]);
-        const float r0 = sub(x[2 * k], sp_lo(hp)), r1 = sub(x[2 * k + 1], sp_hi(hp));   // exact
+        const float r0 = sp_sub(x[2 * k], sp_lo(hp)), r1 = sp_sub(x[2 * k + 1], sp_hi(hp));   // exact
         const uint32_t mp = sp_pack(r0, r1);
-        const float s0 = sub(r0, sp_lo(mp)), s1 = sub(r1, sp_hi(mp));                  // exact
+        const float s0 = sp_sub(r0, sp_lo(mp)), s1 = sp_sub(r1, sp_hi(mp));                  // exact
         h[k] = hp;
         m[k] = mp;
         l[k] = sp_pack(s0, s1);

@@ -10,9 +10,9 @@ namespace rc {
 constexpr int kSpBK = 16;                   // d per ring stage (two per K step)
 constexpr int kSpMaxFused = 5;              // levels the epilogue writes (more: pooled from memory)
 
-// Ring geometry for stage rows TW floats wide (the tile width in w; 16 | TW,
-// TW <= 128) and SL slots (stages).  Even SL: SL / 2 whole K steps, one in
-// use, the rest in flight, refilled a K step at a time at the top of a step.
+// Ring geometry for stage rows TW floats wide (the tile width in w: 128) and
+// SL slots (stages).  SL 4: two whole K steps, one in use, the other in
+// flight, refilled a K step at a time at the top of a step.
 // SL 3: one K step in use plus ONE stage in flight; the two slots a K step
 // read are refilled in the middle of that step, behind a second workgroup
 // barrier after the waves' last fragment read (split_body).  A DMA block
@@ -21,15 +21,11 @@ constexpr int kSpMaxFused = 5;              // levels the epilogue writes (more:
 // 4 (8 TW + 16) / 4 = 16 mod 32 dwords for TW % 16 == 0.
 //   TW 128, SL 4: 66.5 KB -- two workgroups per CU;
 //   TW 128, SL 3: 48.75 KB -- three workgroups per CU (DESIGN.md §3.1c for
-//   which shapes run which);
-//   TW 80, SL 6 / SL 4 (dev A/B, tiles of at most 5 fragments, W <= 160):
-//   61.5 KB, two K steps in flight at the same two workgroups per CU / 41 KB,
-//   three workgroups per CU.  Realtime graph step 61.8 / 61.5 vs 60.7 us:
-//   not kept.
+//   which shapes run which).
+// Rows 80 wide with 6 / 4 slots were measured and not kept.
 template <int TW, int SL>
 struct SpRing {
-    static_assert(TW % 16 == 0 && TW <= 128 && (SL == 3 || (SL % 2 == 0 && SL >= 4)),
-                  "split ring geometry");
+    static_assert(TW == 128 && (SL == 3 || SL == 4), "split ring geometry");
     static constexpr int Blk = 8 * TW + 16;   // bytes per DMA block: 2 rows + 16 B pad
     static constexpr int Op = 8 * Blk;        // one operand tile of a stage: 16 rows
     static constexpr int Slot = 2 * Op;       // F1 + F2
@@ -39,13 +35,7 @@ struct SpRing {
     static constexpr int Pro = SL == 3 ? 3 : 2 * KA;   // stages the prologue issues
 };
 constexpr int kSpStb = 16 * (64 + 4) * 4;     // per-wave epilogue staging (epilogue_swapped, WT 64)
-static_assert(kSpStb <= SpRing<128, 3>::Wave && kSpStb <= SpRing<80, 4>::Wave,
-              "epilogue staging aliases the ring");
-// the pair epilogue (kModePairEpi, dev, wide ring only): two columns of levels
-// 0-2 per wave, at WT = 64
-static_assert(2 * 16 * ((64 + 4) + (32 + 4) + (16 + 4)) * 4 <= SpRing<128, 4>::Wave, "pair staging per wave");
-// levels 0-2 of one column (the fast epilogue), at the narrow ring's WT <= 48
-static_assert(16 * ((48 + 4) + (24 + 4) + (12 + 4)) * 4 <= SpRing<80, 4>::Wave, "staging per wave");
+static_assert(kSpStb <= SpRing<128, 3>::Wave, "epilogue staging aliases the ring");
 
 // One lane's fragment: rows r0..r0+7 (d inside the stage) of w column w of an
 // operand tile at LDS byte address base.  Row d of the tile sits in block
@@ -65,7 +55,7 @@ __device__ __forceinline__ SplitFrag sp_split_raw(const float (&x)[8]) {
         const bf16x8 hb = __builtin_bit_cast(bf16x8, h);
         return SplitFrag{hb, hb, hb};
     }
-    return sp_split<(MODE & kModePackedSub) == 0>(x);
+    return sp_split(x);
 }
 template <int MODE, int TW = 128>
 __device__ __forceinline__ SplitFrag sp_read(const char *base) {

@@ -32,19 +32,6 @@
 
 namespace rc {
 
-
-// First-round stagger: workgroup slot k of a CU (blockIdx / nCU) waits k
-// units before starting, so the co-resident workgroups of a CU sit in
-// different phases (load / MFMA / store) instead of in lockstep; later
-// workgroups inherit the offset when they take a finished slot.
-__device__ __forceinline__ void stagger_start(int bid, int ncu, int unit_sleeps) {
-    const int slot = bid / ncu;
-    if (slot >= 1 && slot <= 2) {
-        const int n = slot * unit_sleeps;
-        for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(127);  // ~8k cycles each
-    }
-}
-
 constexpr int kStageFloats = 64 * 32;  // per-wave LDS staging: one 64x32 fp32 level-1 tile
 
 
@@ -276,7 +263,6 @@ __device__ __forceinline__ void wave_tile(const BuildArgs &a, int row, int b, in
 
 template <bool VEC, int U, int MODE>
 __global__ __launch_bounds__(256) void build_f32_kernel(BuildArgs a, int nwg_total) {
-    if constexpr ((MODE & kModeStagger) != 0) stagger_start(blockIdx.x, 256, a.stagger);
     // one LDS array (guide §5 trap 4a): per wave an 8 KB + 4 KB ping-pong
     // staging image for the pooled levels
     __shared__ __attribute__((aligned(16))) float smem[4][kStageFloats + kStageFloats / 2];
@@ -284,9 +270,7 @@ __global__ __launch_bounds__(256) void build_f32_kernel(BuildArgs a, int nwg_tot
     float *stA = smem[wave], *stB = smem[wave] + kStageFloats;
     const int T = a.tiles_m * a.tiles_n;
     auto tile_body = [&](int v) {
-        // XCD-aware bijective remap (cdna_hip_programming.md §5, "XCD swizzle").
-        const int xcd = v & 7, q = nwg_total >> 3, rr = nwg_total & 7;
-        const int wgid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (v >> 3);
+        const int wgid = xcd_remap(v, nwg_total);
         const int row = wgid / T, tile = wgid - row * T;
         const int tm = tile / a.tiles_n, tn = tile - tm * a.tiles_n;
         const int b = row / a.H, h = row - b * a.H;
@@ -328,11 +312,12 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 // One 16x16x32 operand fragment: two transposed 4-row reads (d = 8g+q and
-// 8g+4+q rows of the image, this lane's 4 columns), i.e. k = 8g .. 8g+7.
-__device__ __forceinline__ bf16x8 read_frag(const char *p) {
+// 8g+4+q rows of an image of `pitch` bytes per row, this lane's 4 columns),
+// i.e. k = 8g .. 8g+7.
+__device__ __forceinline__ bf16x8 read_frag(const char *p, int pitch) {
     typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
     const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(p));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(p + 4 * kImgRow));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(p + 4 * pitch));
     const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     return __builtin_bit_cast(bf16x8, v);
 }
@@ -461,8 +446,8 @@ __device__ __forceinline__ void wave_tile_bf16(const BuildArgs &a, int row, int 
 #pragma unroll
         for (int f = 0; f < 4; ++f) {
             const int colb = (16 * f + 4 * p4) * 2;
-            fa[f] = read_frag(imgA + (8 * g + q) * kImgRow + colb);
-            fb[f] = read_frag(imgB + (8 * g + q) * kImgRow + colb);
+            fa[f] = read_frag(imgA + (8 * g + q) * kImgRow + colb, kImgRow);
+            fb[f] = read_frag(imgB + (8 * g + q) * kImgRow + colb, kImgRow);
         }
 #pragma unroll
         for (int ma = 0; ma < 4; ++ma)
@@ -482,9 +467,7 @@ __global__ __launch_bounds__(256) void build_bf16_kernel(BuildArgs a, int nwg_to
     float *stA = smem[wave], *stB = smem[wave] + kStageFloats;
     char *img = reinterpret_cast<char *>(smem[wave]);
     const int T = a.tiles_m * a.tiles_n;
-    const int v = blockIdx.x;
-    const int xcd = v & 7, q = nwg_total >> 3, rr = nwg_total & 7;
-    const int wgid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (v >> 3);
+    const int wgid = xcd_remap(blockIdx.x, nwg_total);
     const int row = wgid / T, tile = wgid - row * T;
     const int tm = tile / a.tiles_n, tn = tile - tm * a.tiles_n;
     const int b = row / a.H, h = row - b * a.H;
@@ -557,8 +540,6 @@ static_assert(2 * (kRecL0Pad + rec_e0(21) + kRecSlots - kRecL2Slots) <= kRecL0P 
 // for c != 3, the two parts for c = 3 -- three LDS reads per chunk, the same
 // for every lane.  The unit's records are one contiguous run of 8 * rec_nr
 // lines (16 B per lane, 128 B per 8 lanes, written whole).
-typedef unsigned rec_u32x4 __attribute__((ext_vector_type(4)));
-
 template <int MODE, int NL>
 __device__ __forceinline__ void rec_emit_unit(const BuildArgs &a, const char *img, int u, int erow, int em0, int ll) {
     const int c = ll & 7;
@@ -604,9 +585,6 @@ __device__ __forceinline__ void rec_emit_unit(const BuildArgs &a, const char *im
             if (t + b * S < J) {
                 if constexpr ((MODE & kModeRecNoStore) != 0)       // dev timing: gathered, not stored
                     asm volatile("" ::"v"(v[b][0]), "v"(v[b][1]), "v"(v[b][2]), "v"(v[b][3]));
-                else if constexpr ((MODE & kModeRecNT) != 0)       // dev A/B: streaming (non-temporal) stores
-                    __builtin_nontemporal_store(rec_u32x4{v[b][0], v[b][1], v[b][2], v[b][3]},
-                                                reinterpret_cast<rec_u32x4 *>(base + (long long)(t + b * S) * 128));
                 else
                     *reinterpret_cast<uint4 *>(base + (long long)(t + b * S) * 128) =
                         uint4{v[b][0], v[b][1], v[b][2], v[b][3]};
@@ -645,16 +623,6 @@ __device__ __forceinline__ s16x4 tr_read_asm(uint32_t lds_addr) {
     asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(lds_addr), "i"(OFF));
     return v;
 }
-
-// Pitch-parametrised fragment read (see read_frag): rows 8g+q and 8g+4+q.
-__device__ __forceinline__ bf16x8 read_frag_p(const char *p, int pitch) {
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(p));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(p + 4 * pitch));
-    const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, v);
-}
-
 
 // s_waitcnt vmcnt(m) lgkmcnt(0) with m = n rounded down to a multiple of 4,
 // capped at 60 (waiting for more than asked is always safe); the immediate
@@ -699,7 +667,6 @@ __global__ __launch_bounds__(128 * NWN + 128) void build_bf16_ring_kernel(BuildA
     static_assert(!DEFER || FMA == 4, "deferred epilogue: 4 fragments per wave");
     constexpr bool REC = (MODE & kModeRecords) != 0;              // RC_LAYOUT_RECORDS
     static_assert(!REC || DEFER, "records: the deferred epilogue");
-    constexpr bool LEMIT = REC && (MODE & kModeRecLoaderEmit) != 0;   // dev: the loader waves emit
     __shared__ __attribute__((aligned(16)))
     char smem[SL * G::SLOT + (REC ? 2 * kRecImg : NC * (DEFER ? kB16DeferStage : G::STB))];
     typedef __attribute__((address_space(3))) void lds_void;
@@ -854,21 +821,6 @@ __global__ __launch_bounds__(128 * NWN + 128) void build_bf16_ring_kernel(BuildA
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             issue_next();
-            if constexpr (LEMIT) {
-                // dev: this loader wave emits its wave row's units -- unit
-                // st - 1 of the tile before (stage st = 1..8), or unit 7 of
-                // the tile two back at stage 0 of 8-stage tiles
-                const int k = gs / nst, st = gs - k * nst;
-                int ek = -1, eu = 0;
-                if (st >= 1 && st <= 8 && k >= 1) { ek = k - 1; eu = st - 1; }
-                else if (st == 0 && nst == 8 && k >= 2) { ek = k - 2; eu = 7; }
-                if (ek >= 0) {
-                    const B16Tile et = tile_at(ek);
-                    if (et.M0 + 64 * lid < W1)
-                        rec_emit_unit<MODE, 64>(a, smem + SL * G::SLOT + lid * kRecImg, eu, et.row,
-                                                et.M0 + 64 * lid, lane);
-                }
-            }
         }
         if constexpr (REC) {   // the compute waves' last-tile records (rec_write / rec_emit)
 #pragma unroll
@@ -876,17 +828,6 @@ __global__ __launch_bounds__(128 * NWN + 128) void build_bf16_ring_kernel(BuildA
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
-                if constexpr (LEMIT) {
-                    int ek = -1, eu = 0;
-                    if (u == 0 && nst == 8 && ntile_mine >= 2) { ek = ntile_mine - 2; eu = 7; }
-                    else if (u >= 1) { ek = ntile_mine - 1; eu = u - 1; }
-                    if (ek >= 0) {
-                        const B16Tile et = tile_at(ek);
-                        if (et.M0 + 64 * lid < W1)
-                            rec_emit_unit<MODE, 64>(a, smem + SL * G::SLOT + lid * kRecImg, eu, et.row,
-                                                    et.M0 + 64 * lid, lane);
-                    }
-                }
             }
         }
         return;
@@ -1119,9 +1060,9 @@ __global__ __launch_bounds__(128 * NWN + 128) void build_bf16_ring_kernel(BuildA
                 for (int f = 0; f < 4; ++f) { fb[f] = bf16x8{}; asm volatile("" : "+v"(fb[f])); }
             } else {
 #pragma unroll
-                for (int f = 0; f < FMA; ++f) fa[f] = read_frag_p(slot + a_row + 16 * ((a_ch + 2 * f) ^ sw), G::P2);
+                for (int f = 0; f < FMA; ++f) fa[f] = read_frag(slot + a_row + 16 * ((a_ch + 2 * f) ^ sw), G::P2);
 #pragma unroll
-                for (int f = 0; f < 4; ++f) fb[f] = read_frag_p(slot + b_row + 16 * ((b_ch + 2 * f) ^ sw), kB16P1);
+                for (int f = 0; f < 4; ++f) fb[f] = read_frag(slot + b_row + 16 * ((b_ch + 2 * f) ^ sw), kB16P1);
             }
 #pragma unroll
             for (int ma = 0; ma < FMA; ++ma)
@@ -1129,7 +1070,7 @@ __global__ __launch_bounds__(128 * NWN + 128) void build_bf16_ring_kernel(BuildA
                 for (int nb = 0; nb < 4; ++nb)
                     acc[ma][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[ma], fb[nb], acc[ma][nb], 0, 0, 0);
         }
-        if constexpr (REC && !(MODE & (kModeNoStores | kModeRecNoEmit | kModeRecLoaderEmit))) {
+        if constexpr (REC && !(MODE & (kModeNoStores | kModeRecNoEmit))) {
             if (pend && st == 0) {   // unit 7 of the tile held before the current one
                 rec_emit(7, prow, pm0, true);
                 pend = false;
@@ -1141,21 +1082,12 @@ __global__ __launch_bounds__(128 * NWN + 128) void build_bf16_ring_kernel(BuildA
 #pragma unroll
                     for (int u = 0; u <= 8; ++u) {
                         if (st == u) {
-                            if constexpr (!(MODE & (kModeRecNoEmit | kModeRecLoaderEmit))) {
+                            if constexpr (!(MODE & kModeRecNoEmit)) {
                                 if (u >= 1) rec_emit(u - 1, hrow, hm0, hact);
                             }
                             if (u < 8) rec_write(u);
                         }
                     }
-                } else if constexpr ((MODE & kModeSpread) != 0) {   // 8 half-pieces, one per stage at nst = 8
-#pragma unroll
-                    for (int p = 0; p < 8; ++p)
-                        if (((p * nst) >> 3) == st) store_piece(p >> 1, p & 1, (p & 1) + 1);
-                } else if constexpr ((MODE & kModeStagger) != 0) {   // odd waves one stage later
-                    const int off = nst >= 8 ? (wave & 1) : 0;
-#pragma unroll
-                    for (int nb = 0; nb < 4; ++nb)
-                        if (((nb * nst) >> 2) + off == st) store_piece(nb);
                 } else {
 #pragma unroll
                     for (int nb = 0; nb < 4; ++nb)
@@ -1193,7 +1125,7 @@ __global__ __launch_bounds__(128 * NWN + 128) void build_bf16_ring_kernel(BuildA
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-            if constexpr (!(MODE & (kModeRecNoEmit | kModeNoStores | kModeRecLoaderEmit))) {
+            if constexpr (!(MODE & (kModeRecNoEmit | kModeNoStores))) {
                 if (u == 0 && pend) rec_emit(7, prow, pm0, true);
                 if (u >= 1) rec_emit(u - 1, hrow, hm0, hact);
             }
@@ -1238,24 +1170,13 @@ static B16Shape bf16_ring_shape(const BuildArgs &a) {
     return best;
 }
 
-static int device_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-    }
-    return n;
-}
-
 template <int NWN, int FMA, int SL, int MODE, bool DEFER>
-static void launch_bf16_ring_n(const BuildArgs &a, hipStream_t s, int per_cu = 1) {
+static void launch_bf16_ring_n(const BuildArgs &a, hipStream_t s) {
     constexpr int TW = B16Geom<NWN, FMA>::TW;
     const int tiles_m = (a.W1 + 127) / 128, tiles_n = (a.W2 + TW - 1) / TW;
     const long long ntiles = (long long)a.B * a.H * tiles_m * tiles_n;
     if (ntiles <= 0 || ntiles > 0x7FFFFFFF) return;
-    const long long cap = (long long)device_cus() * per_cu;                 // resident workgroups (LDS-bound)
+    const long long cap = device_cus();                                     // resident workgroups (LDS-bound)
     const long long nwg = ntiles < cap ? ntiles : cap;
     // up to 3 fused levels (the default pair layout) keeps the epilogue's
     // level pointers out of the scalar registers the K loop needs
@@ -1413,9 +1334,7 @@ __global__ __launch_bounds__(256) void build_f32_ring_kernel(BuildArgs a, int nw
     c.wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     c.lane = threadIdx.x & 63;
     const int T = a.tiles_m * a.tiles_n;
-    const int v = blockIdx.x;
-    const int xcd = v & 7, q = nwg_total >> 3, rr = nwg_total & 7;
-    const int wgid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (v >> 3);
+    const int wgid = xcd_remap(blockIdx.x, nwg_total);
     const int row = wgid / T, tile = wgid - row * T;
     const int tm = tile / a.tiles_n, tn = tile - tm * a.tiles_n;
     const int b = row / a.H;

@@ -66,7 +66,7 @@ struct SpCtx {
 };
 
 // DMA share of this wave per stage: rows 4w..4w+3 of both tiles, 2 rows
-// (TW / 2 lanes x 16 B: all 64 at TW = 128) per instruction -> 4 instructions
+// (TW / 2 = 64 lanes x 16 B) per instruction -> 4 instructions
 // per stage.
 template <int MODE, int TW, int SL>
 __device__ __forceinline__ void sp_issue(const SpCtx &c, char *smem, int st, int slot) {
@@ -91,13 +91,9 @@ __device__ __forceinline__ void sp_issue(const SpCtx &c, char *smem, int st, int
             offA = d < c.D && c.wA ? c.oA[i] + (uint32_t)st * c.sA : 0xFFFFFF00u;
             offB = d < c.D && c.wB ? c.oB[i] + (uint32_t)st * c.sB : 0xFFFFFF00u;
         }
-        // lanes past the block's 2 TW floats write nothing (EXEC), so the
-        // next block is not overwritten
         if constexpr (!(MODE & kModeNoLoads)) {
-            if (TW == 128 || c.lane < TW / 2) {
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(c.r1, (lds_void *)(sA + (r0 >> 1) * G::Blk), 16, (int)offA, 0, 0, 0);
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(c.r2, (lds_void *)(sB + (r0 >> 1) * G::Blk), 16, (int)offB, 0, 0, 0);
-            }
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(c.r1, (lds_void *)(sA + (r0 >> 1) * G::Blk), 16, (int)offA, 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(c.r2, (lds_void *)(sB + (r0 >> 1) * G::Blk), 16, (int)offB, 0, 0, 0);
         }
     }
 }
@@ -139,8 +135,7 @@ __device__ __forceinline__ void split_body(const SpCtx &c, const BuildArgs &a, c
             // prologue, KA - 2 later, since K step ks + KA - 1 is issued after
             // this wait); WAR: my LDS reads of K step ks - 1 are done.  Barrier.
             const int later = min(ks == 0 ? KA - 1 : KA - 2, nks - 1 - ks);
-            if (KA >= 3 && later >= 2) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory");
-            else if (later >= 1) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
+            if (later >= 1) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         }
         __builtin_amdgcn_s_barrier();
@@ -190,42 +185,16 @@ __device__ __forceinline__ void split_body(const SpCtx &c, const BuildArgs &a, c
             SplitFrag fb[FB];
 #pragma unroll
             for (int n = 0; n < FB; ++n) fb[n] = sp_read<MODE, TW>(pb + 64 * n);
-            if constexpr ((MODE & kModePhasePrio) != 0) {
-                // dev A/B: every fragment read and split first, then all the
-                // MFMAs at raised wave priority, so that the SIMD's other wave
-                // fills the issue slots with its split while these run
-                SplitFrag fa[FA];
 #pragma unroll
-                for (int m = 0; m < FA; ++m) fa[m] = sp_read<MODE, TW>(pa + 64 * m);
-                mid();
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_setprio(3);
+            for (int m = 0; m < FA; ++m) {
+                // the last fragment: its raw dwords, the mid-step barrier
+                // and refill (three slots), then its split
+                float xa[8];
+                sp_read_raw<TW>(pa + 64 * m, xa);
+                if (m == FA - 1) mid();
+                const SplitFrag fa = sp_split_raw<MODE>(xa);
 #pragma unroll
-                for (int m = 0; m < FA; ++m)
-#pragma unroll
-                    for (int n = 0; n < FB; ++n) mma6(acc[m][n], fa[m], fb[n]);
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_setprio(0);
-            } else {
-#pragma unroll
-                for (int m = 0; m < FA; ++m) {
-                    // the last fragment: its raw dwords, the mid-step barrier
-                    // and refill (three slots), then its split
-                    float xa[8];
-                    sp_read_raw<TW>(pa + 64 * m, xa);
-                    if (m == FA - 1) mid();
-                    const SplitFrag fa = sp_split_raw<MODE>(xa);
-                    if constexpr ((MODE & kModeMfmaPrio) != 0) {   // dev A/B: each fragment's MFMAs at raised priority
-                        __builtin_amdgcn_sched_barrier(0);
-                        __builtin_amdgcn_s_setprio(3);
-                    }
-#pragma unroll
-                    for (int n = 0; n < FB; ++n) mma6(acc[m][n], fa, fb[n]);
-                    if constexpr ((MODE & kModeMfmaPrio) != 0) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        __builtin_amdgcn_s_setprio(0);
-                    }
-                }
+                for (int n = 0; n < FB; ++n) mma6(acc[m][n], fa, fb[n]);
             }
         } else {
             mid();
@@ -246,10 +215,10 @@ __device__ __forceinline__ void split_body(const SpCtx &c, const BuildArgs &a, c
         epilogue_sheared<FA>(acc, a, row, c.M0 + c.o1, c.N0 + c.o2, elane,
                              lds_u32(smem + c.wave * G::Wave), w1e < a.W1 ? w1e : a.W1);
     } else if constexpr (FA > 0) {
-        // the compile-time-geometry flushes (fp32 levels 0-2) unless the dev
-        // A/B asks for the generic epilogue: config 2 262.5 vs 281.2 us
+        // the compile-time-geometry flushes (fp32 levels 0-2), not the generic
+        // epilogue: config 2 262.5 vs 281.2 us
         // (profiles/r04/o/build_ablate.log, bit-identical)
-        epilogue_swapped<FA, (MODE & kModeGenericEpi) ? MODE : (MODE | kModeFastEpi), NLM>(
+        epilogue_swapped<FA, MODE | kModeFastEpi, NLM>(
             acc, a, row, c.M0 + c.o1, c.N0 + c.o2, elane,
             lds_u32(smem + c.wave * G::Wave), c.M0 + c.o1 + 16 * FB);
     }
@@ -257,13 +226,8 @@ __device__ __forceinline__ void split_body(const SpCtx &c, const BuildArgs &a, c
 
 template <int FA, int MODE, int NLM, int TW, int SL>
 __device__ __forceinline__ void split_fb(int fb, const SpCtx &c, const BuildArgs &a, char *smem, int row) {
-    if constexpr ((TW / 16 + 1) / 2 >= 4) {            // a wave's share: ceil(TW / 32) fragments
-        if (fb >= 4) {
-            split_body<FA, 4, MODE, NLM, TW, SL>(c, a, smem, row);
-            return;
-        }
-    }
-    if (fb == 3) split_body<FA, 3, MODE, NLM, TW, SL>(c, a, smem, row);
+    if (fb >= 4) split_body<FA, 4, MODE, NLM, TW, SL>(c, a, smem, row);
+    else if (fb == 3) split_body<FA, 3, MODE, NLM, TW, SL>(c, a, smem, row);
     else if (fb == 2) split_body<FA, 2, MODE, NLM, TW, SL>(c, a, smem, row);
     else split_body<FA, 1, MODE, NLM, TW, SL>(c, a, smem, row);
 }
@@ -293,7 +257,7 @@ __global__ __launch_bounds__(256, SL == 3 ? 3 : 2) void build_split_kernel(Build
     c.o1 = 16 * h1 * wm; c.o2 = 16 * h2 * wn;
     c.nst = 2 * ((a.D + 2 * kSpBK - 1) / (2 * kSpBK));   // whole K steps (d >= D reads zeros)
     {
-        // lane -> (row of its 2-row block, 4 columns); lanes >= TW / 2 idle
+        // lane -> (row of its 2-row block, 4 columns)
         const int w = 4 * (c.lane % (TW / 4));
         c.odd = c.lane >= TW / 4;
         c.dr0 = 4 * c.wave + (c.odd ? 1 : 0);
@@ -319,9 +283,8 @@ __global__ __launch_bounds__(256, SL == 3 ? 3 : 2) void build_split_kernel(Build
     const int cw1 = a.W1 - (c.M0 + c.o1), cw2 = a.W2 - (c.N0 + c.o2);
     const int v1 = cw1 <= 0 ? 0 : min(n1, (cw1 + 15) >> 4), v2 = cw2 <= 0 ? 0 : min(n2, (cw2 + 15) >> 4);
     const int fa = v1 == 0 ? 0 : v2, fb = v1;
-    constexpr int FMAX = (TW / 16 + 1) / 2;                // fragments per wave at most (4 or 3)
-    static_assert(FMAX == 3 || FMAX == 4, "split tile width");
-    if (FMAX == 4 && fa >= 4) split_fb<FMAX, MODE, NLM, TW, SL>(fb, c, a, smem, row);
+    static_assert(TW == 128, "split tile width: at most 4 fragments per wave");
+    if (fa >= 4) split_fb<4, MODE, NLM, TW, SL>(fb, c, a, smem, row);
     else if (fa == 3) split_fb<3, MODE, NLM, TW, SL>(fb, c, a, smem, row);
     else if (fa == 2) split_fb<2, MODE, NLM, TW, SL>(fb, c, a, smem, row);
     else if (fa == 1) split_fb<1, MODE, NLM, TW, SL>(fb, c, a, smem, row);
@@ -334,18 +297,8 @@ __global__ __launch_bounds__(256, SL == 3 ? 3 : 2) void build_split_kernel(Build
 // four slots.  A HEURISTIC: measured at 480 (four slots
 // win), 4,320 and 17,856 workgroups (three win) on 256 CUs; nothing between
 // 513 and 4,320 was measured, and a grid of little more than one round may
-// sit on either side.  The CU count is that of the device current at the
-// first call, taken once: every GPU of a node this project runs on is the same.
-static bool sp_ring3(long long nwg) {
-    static const int ncu = [] {
-        int d = 0, n = 0;
-        if (hipGetDevice(&d) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n <= 0)
-            n = 256;
-        return n;
-    }();
-    return nwg > 2LL * ncu;
-}
+// sit on either side.
+static bool sp_ring3(long long nwg) { return nwg > 2LL * device_cus(); }
 
 #ifdef RAFTCORR_DEV
 #include "dev/volume_split_dev.inc"   // ablation modes: libraftcorr_dev.so only

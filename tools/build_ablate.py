@@ -6,7 +6,7 @@ Variants: 'exact' (rc::build_f32_ring_kernel, RC_BUILD_EXACT_F32) and the
 split-bf16 kernel (rc::build_split_kernel) under the dev library's
 RAFTCORR_SPLIT_MODE ablation flags: 0 product, 1 no operand loads, 2 no
 epilogue stores, 4 no MFMAs (sums combine; timing only, wrong values); a
-variant NAME=VALUE sets that dev knob instead (e.g. RAFTCORR_SPLIT_RING=85).
+variant NAME=VALUE sets that dev knob instead (e.g. RAFTCORR_SPLIT_RING=103).
 Prints the median / min microseconds per launch of each variant and the
 range of its per-round medians (the run-to-run spread inside this process).
 """
