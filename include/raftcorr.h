@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define RC_ABI_VERSION 12
+#define RC_ABI_VERSION 13
 
 /* element types */
 #define RC_F32  0
@@ -74,6 +74,23 @@ extern "C" {
  * (torch.channels_last), the same values.  Pair kernel only (2 levels, or 4
  * with level 2 given); RC_EUNSUPPORTED otherwise. */
 #define RC_OUT_CHANNELS_LAST 0x10000
+
+/* Flags OR-ed into the pyr_dtype of rc_corr_lookup_chain / rc_corr_lookup_step
+ * (ABI v13): `out` holds IEEE fp16 (RC_OUT_F16) or bfloat16 (RC_OUT_BF16)
+ * elements instead of fp32, in the same shape and channel order (with or
+ * without RC_OUT_CHANNELS_LAST) -- the dtype a mixed-precision consumer would
+ * cast the fp32 output to.  Each element is the fp32 result of the call
+ * without the flag, rounded to nearest even by the hardware convert: +-inf
+ * stays +-inf, fp16 overflow gives +-inf, fp16 subnormal results are kept
+ * (not flushed), NaN gives a NaN of that type (payload and sign unspecified).
+ * coords1_out and flow_out of rc_corr_lookup_step stay fp32.  Served where
+ * the pair kernel or the records kernel runs: 2 levels, or 4 with level 2
+ * given, or RC_LAYOUT_RECORDS (chain != 0 in the step), any shadow copies.
+ * RC_EUNSUPPORTED before any launch otherwise (the level-1 chain,
+ * RC_LAYOUT_DISPARITY, chain == 0, every other entry point); both flags
+ * together are RC_EINVAL. */
+#define RC_OUT_F16  0x40000
+#define RC_OUT_BF16 0x200000
 
 /* Flag OR-ed into the pyr_dtype of rc_corr_build (ABI v6): run the exact fp32
  * MFMA kernel (v_mfma_f32_16x16x4_f32) for fp32 fmaps and an fp32 pyramid.
@@ -243,10 +260,11 @@ int rc_corr_lookup_conv_backward(const void *const *pyr, const int *widths, cons
  * pool chain for the results to equal rc_corr_lookup's.  pyr_dtype RC_BF16
  * (pair layout only): every level is the bf16-rounded pool of the level below
  * as stored -- what rc_corr_build and rc_corr_pool write for a bf16 pyramid,
- * and what avg_pool2d gives on bf16 tensors.  (ABI v4 added pyr_dtype.) */
+ * and what avg_pool2d gives on bf16 tensors.  (ABI v4 added pyr_dtype.)
+ * out: fp32, or the element type RC_OUT_F16 / RC_OUT_BF16 asks for (ABI v13). */
 int rc_corr_lookup_chain(const void *const *pyr, const int *widths, const long *pyr_ld,
                          int pyr_dtype, int levels, int radius, const float *coords_x,
-                         long coord_batch_stride, int B, int H, int W1, float *out,
+                         long coord_batch_stride, int B, int H, int W1, void *out,
                          void *stream);
 
 /* One iteration of the forward loop's corr step in one launch: the
@@ -259,11 +277,12 @@ int rc_corr_lookup_chain(const void *const *pyr, const int *widths, const long *
  * rc_corr_lookup_chain's kernel (its preconditions apply), else
  * rc_corr_lookup's.  The lookup output is bit-identical to theirs at the
  * updated coordinates; coords1_out and flow_out are bit-identical to the
- * PyTorch ops they replace.  SURVEY.md §8f rank 4. */
+ * PyTorch ops they replace.  SURVEY.md §8f rank 4.  out: fp32, or (chain != 0,
+ * pair or records kernel) the element type RC_OUT_F16 / RC_OUT_BF16 asks for. */
 int rc_corr_lookup_step(const void *const *pyr, const int *widths, const long *pyr_ld,
                         int pyr_dtype, int levels, int radius, int chain,
                         const float *coords1, const float *delta, float *coords1_out,
-                        float *flow_out, int B, int H, int W1, float *out, void *stream);
+                        float *flow_out, int B, int H, int W1, void *out, void *stream);
 
 /* Backward of rc_corr_lookup (model.py:297-316 through grid_sample's input
  * gradient, :275): for every pixel p, level i and tap t, adds

@@ -74,6 +74,22 @@ def _dtype_code(dt):
     raise TypeError(f"raft_stereo_amd: unsupported dtype {dt} (float32 or bfloat16)")
 
 
+def _check_out_dtype(out_dtype):
+    """The lookup output dtype option: None for fp32 (the default), else
+    torch.float16 / torch.bfloat16; anything else raises ValueError."""
+    if out_dtype is None or out_dtype == torch.float32:
+        return None
+    if out_dtype in (torch.float16, torch.bfloat16):
+        return out_dtype
+    raise ValueError(f"CorrBlock1D: out_dtype={out_dtype!r}: None, torch.float32, torch.float16 "
+                     "or torch.bfloat16")
+
+
+def _out_flag(out_dtype):
+    """RC_OUT_F16 / RC_OUT_BF16 for a checked out_dtype (0 for fp32)."""
+    return {None: 0, torch.float16: _lib.RC_OUT_F16, torch.bfloat16: _lib.RC_OUT_BF16}[out_dtype]
+
+
 def _check_fmaps(fmap1, fmap2):
     _require_hip(fmap1, "fmap1")
     _require_hip(fmap2, "fmap2")
@@ -349,12 +365,14 @@ def _chain_args(pyramid, num_levels, shadow=False):
     return lv, ptrs, widths, lds, _dtype_code(dt) | _shadow_flags(shadow, lv)
 
 
-def _lookup_out(B, C, H, W1, device, channels_last):
-    """(B, C, H, W1) fp32 lookup output; channels_last: NHWC memory order
-    (the C-ABI's RC_OUT_CHANNELS_LAST), same shape and values."""
+def _lookup_out(B, C, H, W1, device, channels_last, dtype=None):
+    """(B, C, H, W1) lookup output, fp32 unless ``dtype`` (a checked
+    out_dtype) says otherwise; channels_last: NHWC memory order (the C-ABI's
+    RC_OUT_CHANNELS_LAST), same shape and values."""
+    dtype = torch.float32 if dtype is None else dtype
     if channels_last:
-        return torch.empty((B, H, W1, C), dtype=torch.float32, device=device).permute(0, 3, 1, 2)
-    return torch.empty((B, C, H, W1), dtype=torch.float32, device=device)
+        return torch.empty((B, H, W1, C), dtype=dtype, device=device).permute(0, 3, 1, 2)
+    return torch.empty((B, C, H, W1), dtype=dtype, device=device)
 
 
 def _pair_layout(pyramid, num_levels):
@@ -362,21 +380,28 @@ def _pair_layout(pyramid, num_levels):
     return num_levels == 2 or (num_levels == 4 and len(pyramid) > 2 and pyramid[2] is not None)
 
 
-def lookup_chain(pyramid, coords, num_levels, radius, shadow=False, channels_last=False):
+def lookup_chain(pyramid, coords, num_levels, radius, shadow=False, channels_last=False, out_dtype=None):
     """rc_corr_lookup_chain: same result as :func:`lookup` for a pyramid whose
     levels are the avg-pool chain of level 0 (what :func:`build_pyramid`
     writes).  Entries may be None: with 2 levels, or 4 levels and level 2
     present, the kernel reads levels 0 and 2 and derives 1 and 3; otherwise it
-    reads levels 0 and 1 and derives the rest (include/raftcorr.h)."""
+    reads levels 0 and 1 and derives the rest (include/raftcorr.h).
+    ``out_dtype`` (torch.float16 / torch.bfloat16): the pair kernel writes the
+    output in that dtype (RC_OUT_F16 / RC_OUT_BF16); the level-1 chain writes
+    fp32 and the cast follows -- the same values either way."""
     x, cbs = _check_coords(pyramid, coords)
     B, _, H, W1 = coords.shape
-    cl = channels_last and _pair_layout(pyramid, num_levels)
-    out = _lookup_out(B, num_levels * (2 * radius + 1), H, W1, coords.device, cl)
+    od = _check_out_dtype(out_dtype)
+    pair = _pair_layout(pyramid, num_levels)
+    cl = channels_last and pair
+    out = _lookup_out(B, num_levels * (2 * radius + 1), H, W1, coords.device, cl, od if pair else None)
     if B * H * W1 == 0:
-        return out
+        return out if od is None else out.to(od)
     keep, ptrs, widths, lds, dt = _chain_args(pyramid, num_levels, shadow)
     if cl:
         dt |= _lib.RC_OUT_CHANNELS_LAST
+    if pair:
+        dt |= _out_flag(od)
     with torch.cuda.device(coords.device):
         rc = _lib.lib().rc_corr_lookup_chain(
             ptrs, widths, lds, dt, num_levels, radius, x.data_ptr(), cbs, B, H, W1,
@@ -384,7 +409,7 @@ def lookup_chain(pyramid, coords, num_levels, radius, shadow=False, channels_las
     _lib.check(rc, "rc_corr_lookup_chain")
     if channels_last and not cl:
         out = out.contiguous(memory_format=torch.channels_last)
-    return out
+    return out if od is None else out.to(od)     # no copy where the kernel wrote od
 
 
 # ------------------------------------------------- disparity-major layout
@@ -586,20 +611,23 @@ def _check_records_coords(rec, coords):
         raise RuntimeError("CorrBlock1D: coords and pyramid on different devices")
 
 
-def lookup_records(rec, coords, radius, W2, channels_last=False):
+def lookup_records(rec, coords, radius, W2, channels_last=False, out_dtype=None):
     """rc_corr_lookup_chain with RC_LAYOUT_RECORDS: the pair kernel's
-    results (bit for bit) from the records, one 128-B line per pixel."""
+    results (bit for bit) from the records, one 128-B line per pixel.
+    ``out_dtype``: torch.float16 / torch.bfloat16 output, written by the kernel."""
     _check_records_coords(rec, coords)
     B, _, H, W1 = coords.shape
     x = coords[:, 0]
     if x.stride(2) != 1 or x.stride(1) != W1:
         x = x.contiguous()
     cbs = x.stride(0) if B > 1 else H * W1
-    out = _lookup_out(B, 4 * (2 * radius + 1), H, W1, coords.device, channels_last)
+    od = _check_out_dtype(out_dtype)
+    out = _lookup_out(B, 4 * (2 * radius + 1), H, W1, coords.device, channels_last, od)
     if B * H * W1 == 0:
         return out
     ptrs, widths, lds = _records_args(rec, W2)
-    dt = _lib.RC_BF16 | _lib.RC_LAYOUT_RECORDS | (_lib.RC_OUT_CHANNELS_LAST if channels_last else 0)
+    dt = (_lib.RC_BF16 | _lib.RC_LAYOUT_RECORDS | (_lib.RC_OUT_CHANNELS_LAST if channels_last else 0)
+          | _out_flag(od))
     with torch.cuda.device(coords.device):
         rc = _lib.lib().rc_corr_lookup_chain(ptrs, widths, lds, dt, 4, radius, x.data_ptr(), cbs, B, H, W1,
                                              out.data_ptr(), _stream(coords.device))
@@ -895,7 +923,9 @@ class _LookupFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         (coords,) = ctx.saved_tensors
-        ctx.state.accumulate(coords, grad_out)
+        # an fp16 / bf16 output (out_dtype) hands back a gradient of that
+        # dtype: widened here, the level gradients are fp32 as ever
+        ctx.state.accumulate(coords, grad_out.float())
         # the build node only needs SOME defined gradient on its token: the
         # first lookup node to run hands over one zero, the others None (no
         # fill and no add kernel per call)
@@ -941,7 +971,19 @@ class CorrBlock1D:
     def __init__(self, fmap1, fmap2, num_levels=4, radius=4, *, pyramid_dtype=None,
                  lazy_levels=None, shadow=None, channels_last=False, low_latency=False,
                  grad_shadow=None, exact_f32=False, grad_deferred=None, layout="rows",
-                 check_finite=False):
+                 check_finite=False, out_dtype=None):
+        # out_dtype: the dtype of the lookup output --
+        # None / torch.float32 (the reference's), or torch.float16 /
+        # torch.bfloat16 for a consumer that would cast it anyway (the update
+        # block under autocast).  The values are the fp32 output's rounded to
+        # nearest even, i.e. ``self(coords).to(out_dtype)`` bit for bit.
+        # Where the pair or the records kernel serves the block it writes that
+        # dtype itself (half the output bytes, no cast kernel); everywhere
+        # else (3 levels, low_latency, layout="disparity", a replaced
+        # corr_pyramid, radius > 4) the fp32 kernel runs and the cast follows.
+        # Read at call time; refused here, before the build is paid for.
+        _check_out_dtype(out_dtype)
+        self.out_dtype = out_dtype
         self.num_levels = num_levels
         self.radius = radius
         # check_finite (opt-in): the split-bf16 default gives NaN
@@ -1170,15 +1212,20 @@ class CorrBlock1D:
         return self.corr_pyramid[:L]
 
     def _lookup(self, coords):
+        od = _check_out_dtype(self.out_dtype)
         if self._records is not None:
-            return lookup_records(self._records, coords, self.radius, self._shape[3], self.channels_last)
-        if self._sheared is not None:
-            return lookup_sheared(self._sheared, coords, self.num_levels, self.radius, self._shape[3])
-        if self._chain:
+            return lookup_records(self._records, coords, self.radius, self._shape[3], self.channels_last, od)
+        if self._chain and self._sheared is None:
             return lookup_chain(self._levels, coords, self.num_levels, self.radius, self._shadow,
-                                self.channels_last)
-        out = lookup(self._read_levels(), coords, self.num_levels, self.radius)
-        return out.contiguous(memory_format=torch.channels_last) if self.channels_last else out
+                                self.channels_last, od)
+        # kernels that write fp32 only: the cast follows (memory format kept)
+        if self._sheared is not None:
+            out = lookup_sheared(self._sheared, coords, self.num_levels, self.radius, self._shape[3])
+        else:
+            out = lookup(self._read_levels(), coords, self.num_levels, self.radius)
+            if self.channels_last:
+                out = out.contiguous(memory_format=torch.channels_last)
+        return out if od is None else out.to(od)
 
     def __call__(self, coords):
         if self._token is not None and torch.is_grad_enabled():
@@ -1222,10 +1269,14 @@ class CorrBlock1D:
             raise RuntimeError("lookup_step: out must be a contiguous fp32 (B, 2, H, W1) tensor")
         flow = torch.empty_like(c1)
         L, r = self.num_levels, self.radius
-        cl = self.channels_last and self._chain and (self._records is not None or _pair_layout(self._levels, L))
-        corr = _lookup_out(B, L * (2 * r + 1), H, W1, c1.device, cl)
+        # the pair / records kernel serves the step: channels-last and the
+        # out_dtype are written by the kernel; else fp32 NCHW, converted after
+        pair = self._chain and (self._records is not None or _pair_layout(self._levels, L))
+        cl = self.channels_last and pair
+        od = _check_out_dtype(self.out_dtype)
+        corr = _lookup_out(B, L * (2 * r + 1), H, W1, c1.device, cl, od if pair else None)
         if B * H * W1 == 0:
-            return corr, new, flow
+            return (corr if od is None else corr.to(od)), new, flow
         if self._records is not None:
             ptrs, widths, lds = _records_args(self._records, self._shape[3])
             dt = _lib.RC_BF16 | _lib.RC_LAYOUT_RECORDS
@@ -1235,6 +1286,8 @@ class CorrBlock1D:
             keep, ptrs, widths, lds, dt = _level_args(self._read_levels(), L)
         if cl:
             dt |= _lib.RC_OUT_CHANNELS_LAST
+        if pair:
+            dt |= _out_flag(od)
         with torch.cuda.device(c1.device):
             rc = _lib.lib().rc_corr_lookup_step(
                 ptrs, widths, lds, dt, L, r, int(self._chain), c1.data_ptr(),
@@ -1243,12 +1296,14 @@ class CorrBlock1D:
         _lib.check(rc, "rc_corr_lookup_step")
         if self.channels_last and not cl:
             corr = corr.contiguous(memory_format=torch.channels_last)
-        return corr, new, flow
+        return (corr if od is None else corr.to(od)), new, flow
 
     def lookup_convc1(self, coords, weight, bias=None, relu=True, differentiable=False):
         """``relu(convc1(self(coords)))`` in one launch:
         the motion encoder's first layer (model.py:199, :206) fused into the
         lookup, so the (B, L(2r+1), H, W1) correlation never reaches HBM.
+        ``out_dtype`` does not apply: no correlation is written, and the
+        result is convc1's fp32 output.
 
         ``differentiable=False`` is inference-only and raises when gradients
         are being recorded.  ``differentiable=True`` records an autograd node

@@ -30,22 +30,32 @@ int hip_rc(hipError_t e, const char *what) {
     return fail(RC_EHIP, "%s: %s", what, hipGetErrorString(e));
 }
 
+constexpr int RC_OUT_HALF = RC_OUT_F16 | RC_OUT_BF16;
+// LookupArgs::out_dt of a pyr_dtype (checked: not both flags)
+int out_dt_of(int pyr_dtype) { return (pyr_dtype & RC_OUT_F16) ? 1 : (pyr_dtype & RC_OUT_BF16) ? 2 : 0; }
+
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // RC_SHADOW (ABI v5): byte offset from a stored level's base to its copy.
 long long shadow_offset(long long rows, long long ld, int esize) { return RC_SHADOW_OFFSET(rows, ld, esize); }
 
 // pyr_dtype bits an entry point accepts: the element type (low byte), the
-// RC_SHADOW_LEVEL bits and, where the pair kernel serves it, RC_OUT_CHANNELS_LAST.
+// RC_SHADOW_LEVEL bits and, where the pair kernel serves it, RC_OUT_CHANNELS_LAST
+// and RC_OUT_F16 / RC_OUT_BF16 (allow_cl: the two lookup entry points that reach it).
 int check_flags(const char *who, int pyr_dtype, bool allow_cl, bool build = false, bool allow_disp = false,
                 bool allow_rec = false) {
-    const unsigned known = 0xFFu | RC_SHADOW | (allow_cl ? (unsigned)RC_OUT_CHANNELS_LAST : 0u) |
+    const unsigned known = 0xFFu | RC_SHADOW | (allow_cl ? (unsigned)(RC_OUT_CHANNELS_LAST | RC_OUT_HALF) : 0u) |
                            (build ? (unsigned)RC_BUILD_EXACT_F32 : 0u) |
                            (allow_disp ? (unsigned)RC_LAYOUT_DISPARITY : 0u) |
                            (allow_rec ? (unsigned)RC_LAYOUT_RECORDS : 0u);
     if (!allow_cl && (pyr_dtype & RC_OUT_CHANNELS_LAST))
         return fail(RC_EUNSUPPORTED, "%s: RC_OUT_CHANNELS_LAST is only defined for "
                     "rc_corr_lookup_chain / rc_corr_lookup_step", who);
+    if (!allow_cl && (pyr_dtype & RC_OUT_HALF))
+        return fail(RC_EUNSUPPORTED, "%s: RC_OUT_F16 / RC_OUT_BF16 are only defined for "
+                    "rc_corr_lookup_chain / rc_corr_lookup_step", who);
+    if ((pyr_dtype & RC_OUT_HALF) == RC_OUT_HALF)
+        return fail(RC_EINVAL, "%s: RC_OUT_F16 and RC_OUT_BF16 exclude each other", who);
     if (!allow_disp && (pyr_dtype & RC_LAYOUT_DISPARITY))
         return fail(RC_EUNSUPPORTED, "%s: RC_LAYOUT_DISPARITY is only defined for "
                     "rc_corr_build / rc_corr_lookup_chain", who);
@@ -219,7 +229,7 @@ namespace {
 // Shared validation of the lookup entry points; fills `a` or returns an error.
 int prep_lookup(const char *who, const void *const *pyr, const int *widths, const long *pyr_ld,
                 int pyr_dtype, int levels, int radius, const float *coords_x,
-                long coord_batch_stride, int B, int H, int W1, const float *out, rc::LookupArgs &a,
+                long coord_batch_stride, int B, int H, int W1, const void *out, rc::LookupArgs &a,
                 bool *empty, bool allow_null = false) {
     *empty = false;
     const bool disp = (pyr_dtype & RC_LAYOUT_DISPARITY) != 0;     // rows of W1 (or more) per diagonal
@@ -352,7 +362,7 @@ extern "C" int rc_corr_lookup(const void *const *pyr, const int *widths, const l
 
 extern "C" int rc_corr_lookup_chain(const void *const *pyr, const int *widths, const long *pyr_ld,
                                     int pyr_dtype, int levels, int radius, const float *coords_x,
-                                    long coord_batch_stride, int B, int H, int W1, float *out,
+                                    long coord_batch_stride, int B, int H, int W1, void *out,
                                     void *stream) {
     g_err[0] = 0;
     rc::LookupArgs a;
@@ -362,6 +372,7 @@ extern "C" int rc_corr_lookup_chain(const void *const *pyr, const int *widths, c
                          coords_x, coord_batch_stride, B, H, W1, out, a, &empty, true);
     if (rc) return rc;
     const bool cl = (pyr_dtype & RC_OUT_CHANNELS_LAST) != 0;
+    const int out_dt = out_dt_of(pyr_dtype);
     const bool disp = (pyr_dtype & RC_LAYOUT_DISPARITY) != 0;
     const bool rec = (pyr_dtype & RC_LAYOUT_RECORDS) != 0;
     const bool shadowed = ((unsigned)pyr_dtype & RC_SHADOW) != 0;
@@ -379,9 +390,13 @@ extern "C" int rc_corr_lookup_chain(const void *const *pyr, const int *widths, c
                     "(2 levels, or 4 with level 2 given)");
     if (cl && !pair)
         return fail(RC_EUNSUPPORTED, "rc_corr_lookup_chain: RC_OUT_CHANNELS_LAST needs the pair layout");
+    if (out_dt && (!pair || disp))
+        return fail(RC_EUNSUPPORTED, "rc_corr_lookup_chain: RC_OUT_F16 / RC_OUT_BF16 need the pair layout "
+                    "(2 levels, or 4 with level 2 given) in rows or records");
     if (empty) return RC_OK;
-    a.out = out;
+    a.out = static_cast<float *>(out);
     a.out_cl = cl;
+    a.out_dt = out_dt;
     if (!rec && (rc = chain_strides("rc_corr_lookup_chain", a, pair, pyr_dtype == RC_BF16))) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     return hip_rc(pair ? rc_launch_lookup_pair(a, radius, pyr_dtype == RC_BF16, s)
@@ -392,7 +407,7 @@ extern "C" int rc_corr_lookup_chain(const void *const *pyr, const int *widths, c
 extern "C" int rc_corr_lookup_step(const void *const *pyr, const int *widths, const long *pyr_ld,
                                    int pyr_dtype, int levels, int radius, int chain,
                                    const float *coords1, const float *delta, float *coords1_out,
-                                   float *flow_out, int B, int H, int W1, float *out,
+                                   float *flow_out, int B, int H, int W1, void *out,
                                    void *stream) {
     g_err[0] = 0;
     rc::LookupArgs a;
@@ -400,10 +415,21 @@ extern "C" int rc_corr_lookup_step(const void *const *pyr, const int *widths, co
     if (int e = check_flags("rc_corr_lookup_step", pyr_dtype, true, false, false, true)) return e;
     const bool rec = (pyr_dtype & RC_LAYOUT_RECORDS) != 0;
     const bool shadowed = ((unsigned)pyr_dtype & RC_SHADOW) != 0;
+    const int out_dt = out_dt_of(pyr_dtype);
     if (rec && !chain) return fail(RC_EUNSUPPORTED, "rc_corr_lookup_step: RC_LAYOUT_RECORDS needs chain != 0");
+    if (out_dt && !chain)
+        return fail(RC_EUNSUPPORTED, "rc_corr_lookup_step: RC_OUT_F16 / RC_OUT_BF16 need chain != 0");
     int rc = prep_lookup("rc_corr_lookup_step", pyr, widths, pyr_ld, pyr_dtype, levels, radius,
                          coords1, 2L * H * W1, B, H, W1, out, a, &empty, chain != 0);
-    if (rc || empty) return rc;
+    if (rc) return rc;
+    if (out_dt) {   // refused whatever the size: the kernel that would serve the call decides
+        bool p = false;
+        if ((rc = chain_kind("rc_corr_lookup_step", pyr, widths, levels, radius, &p, rec))) return rc;
+        if (!p)
+            return fail(RC_EUNSUPPORTED, "rc_corr_lookup_step: RC_OUT_F16 / RC_OUT_BF16 need the pair layout "
+                        "(2 levels, or 4 with level 2 given) in rows or records");
+    }
+    if (empty) return RC_OK;
     const bool cl = (pyr_dtype & RC_OUT_CHANNELS_LAST) != 0;
     pyr_dtype &= 0xFF;
     if (!coords1_out || !flow_out)
@@ -420,8 +446,9 @@ extern "C" int rc_corr_lookup_step(const void *const *pyr, const int *widths, co
     }
     if (cl && !pair)
         return fail(RC_EUNSUPPORTED, "rc_corr_lookup_step: RC_OUT_CHANNELS_LAST needs the pair layout");
-    a.out = out;
+    a.out = static_cast<float *>(out);
     a.out_cl = cl;
+    a.out_dt = out_dt;
     a.step = 1;
     a.W1 = W1;
     a.delta = delta;

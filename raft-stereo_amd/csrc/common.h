@@ -166,6 +166,9 @@ struct LookupArgs {
     long long shk[kMaxLevels];
     // RC_LAYOUT_RECORDS (ABI v10): lvl[0] = the records, rec_nr per pixel row
     int rec_nr;
+    // RC_OUT_F16 / RC_OUT_BF16 (ABI v13): out holds 1 = fp16, 2 = bf16 elements
+    // (pair and records kernels only, lookup_half.hip); 0 = fp32
+    int out_dt;
 };
 
 // Backward of the lookup: level gradients (fp32, row stride ld[i] % 4 == 0).
@@ -253,6 +256,8 @@ hipError_t rc_launch_lookup_conv_bwd(const rc::LookupArgs &a, int radius, int py
                                      float *workspace, hipStream_t s);
 hipError_t rc_launch_lookup_chain(const rc::LookupArgs &a, int radius, hipStream_t s);
 hipError_t rc_launch_lookup_pair(const rc::LookupArgs &a, int radius, int pyr_bf16, hipStream_t s);
+// the pair / records kernels with a.out_dt != 0 (called by rc_launch_lookup_pair; lookup_half.hip)
+hipError_t rc_launch_lookup_pair_half(const rc::LookupArgs &a, int radius, int pyr_bf16, hipStream_t s);
 hipError_t rc_launch_lookup_bwd(const rc::LookupBwdArgs &a, int radius, hipStream_t s);
 // fills a.pix / rowbase / S / lds_floats from W, radius, levels
 hipError_t rc_launch_lookup_bwd_calls(rc::LookupBwdCallsArgs &a, int radius, int levels, hipStream_t s);

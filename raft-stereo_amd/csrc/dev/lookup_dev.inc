@@ -14,7 +14,7 @@ static hipError_t dev_launch_pair(const LookupArgs &a, int bf16, hipStream_t s) 
         return hipErrorNotSupported;
     } else {
         const int v = dev_knob("RAFTCORR_LOOKUP_VARIANT");
-        if (a.shk[0]) return hipErrorNotSupported;
+        if (a.shk[0] || a.out_dt) return hipErrorNotSupported;   // fp16 / bf16 output: the product kernel
         if (a.levels != 4 || v < 201 || v > 211) return hipErrorNotSupported;
         const unsigned nblk = (unsigned)((a.P + 255) / 256);
 #define RC_PAIR(...)                                                                              \
@@ -82,7 +82,7 @@ static hipError_t dev_launch_conv(const LookupArgs &a, int bf16, const float *w,
 template <int R>
 static hipError_t dev_launch_records(const LookupArgs &a, hipStream_t s) {
     const int v = dev_knob("RAFTCORR_REC_LOOKUP");
-    if (v < 1 || v > 9 || !a.out_cl) return hipErrorNotSupported;
+    if (v < 1 || v > 9 || !a.out_cl || a.out_dt) return hipErrorNotSupported;   // fp16 / bf16 output: the product kernel
     const unsigned nblk = (unsigned)((a.P + 255) / 256);
     if (v == 1) hipLaunchKernelGGL((lookup_records_kernel<R, true, 1>), dim3(nblk), dim3(256), 0, s, a);
     else if (v == 2) hipLaunchKernelGGL((lookup_records_kernel<R, true, 2>), dim3(nblk), dim3(256), 0, s, a);

@@ -233,9 +233,18 @@ class BasicMultiUpdateBlock(nn.Module):
 class RAFTStereo(nn.Module):
     """model.py:335-383 with the correlation block pluggable (``corr_block``)."""
 
-    def __init__(self, args, corr_block=None, fuse_convc1=False, fuse_step=False):
+    def __init__(self, args, corr_block=None, fuse_convc1=False, fuse_step=False, corr_out_dtype=None):
         super().__init__()
         self.args = args
+        # corr_out_dtype (DESIGN.md §3.2j): the lookup output's dtype.  None:
+        # fp32, which convc1 casts under autocast.  "autocast": the autocast
+        # dtype when args.mixed_precision runs on a GPU, so the lookup writes
+        # what convc1 reads (same values, no cast kernel); fp32 otherwise.  A
+        # torch.dtype is passed to the corr block as out_dtype.
+        if not (corr_out_dtype is None or corr_out_dtype == "autocast"
+                or isinstance(corr_out_dtype, torch.dtype)):
+            raise ValueError(f"RAFTStereo: corr_out_dtype={corr_out_dtype!r}: None, 'autocast' or a torch.dtype")
+        self.corr_out_dtype = corr_out_dtype
         context_dims = args.hidden_dims
         self.cnet = BasicEncoder(output_dim=[args.hidden_dims, context_dims], norm_fn="batch",
                                  downsample=args.n_downsample)
@@ -262,6 +271,15 @@ class RAFTStereo(nn.Module):
         dev = "cuda" if torch.cuda.is_available() else "cpu"
         return torch.autocast(dev, dtype=dtype, enabled=enabled and dev == "cuda")
 
+    def _corr_kwargs(self):
+        """The out_dtype keyword for the corr block -- only when the option is
+        set, so a ``corr_block`` with the reference's signature keeps working."""
+        od = self.corr_out_dtype
+        if od == "autocast":
+            on = bool(self.args.mixed_precision) and torch.cuda.is_available()
+            od = getattr(self.args, "autocast_dtype", torch.float16) if on else None
+        return {} if od is None else {"out_dtype": od}
+
     def features(self, image1, image2):
         """Encoders (stay on PyTorch ops): fmaps for the corr path + GRU state."""
         image1 = (2 * (image1 / 255.0) - 1.0).contiguous()
@@ -284,7 +302,8 @@ class RAFTStereo(nn.Module):
         when grad is enabled."""
         a = self.args
         fmap1, fmap2, net_list, inp_list = self.features(image1, image2)
-        corr_fn = self.corr_block(fmap1, fmap2, radius=a.corr_radius, num_levels=a.corr_levels)
+        corr_fn = self.corr_block(fmap1, fmap2, radius=a.corr_radius, num_levels=a.corr_levels,
+                                  **self._corr_kwargs())
         coords0, coords1 = self.initialize_flow(net_list[0])
         if flow_init is not None:
             coords1 = coords1 + flow_init
