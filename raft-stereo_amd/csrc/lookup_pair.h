@@ -71,6 +71,7 @@ struct PairSpan {
     static constexpr int NC = (NS + EPC - 2 + EPC - 1) / EPC;
     uint32_t q[NC][4];                                // raw chunks
     float m, n;                                       // window centres of the odd / even level
+    float xe[4];                                      // x' of taps -R, +R of the even, then the odd level
     int sh;                                           // span start - chunk base (elements)
     bool inwin, valid;
     // element e of the loaded chunks, as fp32
@@ -84,21 +85,33 @@ struct PairSpan {
     }
 };
 
-// Exact element range [f, l] (clipped to [0, W-1]) the taps of one level read.
-template <int R>
-__device__ __forceinline__ void tap_span(float xl, int W, int &f, int &l) {
-    const float Wm1 = (float)(W - 1), half = Wm1 / 2.0f;
-    const DivRN dv = div_prep(Wm1);
-    const float pa = ((div_rn(2.0f * ((float)(-R) + xl), dv) - 1.0f) + 1.0f) * half;
-    const float pb = ((div_rn(2.0f * ((float)R + xl), dv) - 1.0f) + 1.0f) * half;
-    f = max((int)floorf(pa), 0);
-    l = min((int)floorf(pb) + 1, W - 1);
+// The sampler's per-level constants: Wm1 = W - 1, half = Wm1 / 2 and the
+// Markstein divisor {Wm1, RN(1 / Wm1)}.
+struct LevelConsts {
+    float Wm1, half;
+    DivRN dv;
+};
+__device__ __forceinline__ LevelConsts level_consts(const LookupArgs &a, int i) {
+    const float Wm1 = (float)(a.W[i] - 1);
+    return LevelConsts{Wm1, Wm1 / 2.0f, div_prep(Wm1)};
 }
 
-template <int R, bool BF16 = false>
-__device__ __forceinline__ void issue_pair(PairSpan<R, BF16> &ps, const LookupArgs &a, int lo, float x,
-                                           long long pblk, long long lrow) {
-    typedef PairSpan<R, BF16> PS;
+// x' of tap k of a level at x_l: the reference's normalise / unnormalise
+// round trip (lookup.hip), fp32 op for op.
+__device__ __forceinline__ float tap_xp(float xl, int k, const LevelConsts &c) {
+    const float xt = (float)k + xl;
+    const float xn = div_rn(2.0f * xt, c.dv) - 1.0f;
+    return (xn + 1.0f) * c.half;
+}
+
+// The geometry of one pair's span for x: the window centres, and the exact
+// element range [lo_e, hi_e] of level lo that the taps of both levels read
+// (clipped to the rows; empty as lo_e > hi_e).  The x' of each level's two
+// edge taps, which bound that range, are kept in ps.xe: window_taps takes
+// them from there instead of evaluating them again.
+template <int R, bool BF16>
+__device__ __forceinline__ void plan_pair(PairSpan<R, BF16> &ps, const LookupArgs &a, int lo, float x,
+                                          int &lo_e, int &hi_e) {
     const int Wlo = a.W[lo], Whi = a.W[lo + 1];
     const float xlo = x / (float)(1 << lo), xhi = x / (float)(2 << lo);
     // false for NaN; outside it every tap of both levels is zero padding
@@ -107,14 +120,36 @@ __device__ __forceinline__ void issue_pair(PairSpan<R, BF16> &ps, const LookupAr
     ps.n = ps.inwin ? floorf(xlo) : 0.0f;
     const int dd = (int)ps.n - 2 * (int)ps.m;
     ps.valid = ps.inwin && (dd == 0 || dd == 1);      // a subnormal x can break it
-    int lo_e = 0x7FFFFFFF, hi_e = -1;
-    if (ps.inwin) {
-        int f, l;
-        tap_span<R>(xlo, Wlo, f, l);
+    const LevelConsts clo = level_consts(a, lo), chi = level_consts(a, lo + 1);
+    ps.xe[0] = tap_xp(xlo, -R, clo);
+    ps.xe[1] = tap_xp(xlo, R, clo);
+    ps.xe[2] = tap_xp(xhi, -R, chi);
+    ps.xe[3] = tap_xp(xhi, R, chi);
+    lo_e = 0x7FFFFFFF;
+    hi_e = -1;
+    if (ps.inwin) {    // integer casts of in-window (finite, bounded) values only
+        int f = max((int)floorf(ps.xe[0]), 0), l = min((int)floorf(ps.xe[1]) + 1, Wlo - 1);
         if (f <= l) { lo_e = f; hi_e = l; }
-        tap_span<R>(xhi, Whi, f, l);
+        f = max((int)floorf(ps.xe[2]), 0);
+        l = min((int)floorf(ps.xe[3]) + 1, Whi - 1);
         if (f <= l) { lo_e = min(lo_e, 2 * f); hi_e = max(hi_e, 2 * l + 1); }
     }
+}
+
+// The loads of one pair's span: the buffer resource and the byte offset of
+// each 16-B chunk (an out-of-range offset where the taps read none of it).
+template <int R, bool BF16>
+struct PairLoads {
+    __amdgpu_buffer_rsrc_t rs;
+    int off[PairSpan<R, BF16>::NC];
+};
+
+template <int R, bool BF16 = false>
+__device__ __forceinline__ PairLoads<R, BF16> plan_pair_loads(PairSpan<R, BF16> &ps, const LookupArgs &a, int lo,
+                                                              float x, long long pblk, long long lrow) {
+    typedef PairSpan<R, BF16> PS;
+    int lo_e, hi_e;
+    plan_pair<R, BF16>(ps, a, lo, x, lo_e, hi_e);
     const int sa = 2 * ((int)ps.m - R - 1);
     const int ea = sa & ~(PS::EPC - 1);
     ps.sh = sa - ea;
@@ -124,7 +159,8 @@ __device__ __forceinline__ void issue_pair(PairSpan<R, BF16> &ps, const LookupAr
     // line; each lane reads its span from the copy in which it touches fewer
     // lines (same values either way).  The resource then spans both copies.
     const long long shb = a.shadow[lo];
-    const auto rs = make_rsrc(lvl + pblk * ld * PS::ES, clamp_bytes((a.P - pblk) * ld * PS::ES + shb));
+    PairLoads<R, BF16> pl;
+    pl.rs = make_rsrc(lvl + pblk * ld * PS::ES, clamp_bytes((a.P - pblk) * ld * PS::ES + shb));
     uint32_t phase = 0;
     if (shb != 0 && lo_e <= hi_e) {
         const unsigned long long b0 =
@@ -141,8 +177,16 @@ __device__ __forceinline__ void issue_pair(PairSpan<R, BF16> &ps, const LookupAr
         // lo_e >= 0 and hi_e < Wlo: a loaded chunk starts inside the row and
         // ends inside its 16-B padded extent (ld % EPC == 0)
         const bool ok = cs <= hi_e && cs + PS::EPC - 1 >= lo_e;
-        const auto v = __builtin_amdgcn_raw_buffer_load_b128(
-            rs, ok ? (int)((uint32_t)((lrow * ld + cs) * PS::ES) + phase) : (int)0xFFFFFF00u, 0, 0);
+        pl.off[k] = ok ? (int)((uint32_t)((lrow * ld + cs) * PS::ES) + phase) : (int)0xFFFFFF00u;
+    }
+    return pl;
+}
+
+template <int R, bool BF16>
+__device__ __forceinline__ void load_pair(PairSpan<R, BF16> &ps, const PairLoads<R, BF16> &pl) {
+#pragma unroll
+    for (int k = 0; k < PairSpan<R, BF16>::NC; ++k) {
+        const auto v = __builtin_amdgcn_raw_buffer_load_b128(pl.rs, pl.off[k], 0, 0);
 #pragma unroll
         for (int c = 0; c < 4; ++c) ps.q[k][c] = v[c];
     }
@@ -159,28 +203,30 @@ __device__ __forceinline__ void issue_pair(PairSpan<R, BF16> &ps, const LookupAr
 // so x0 = floor(xp) is nt - 1, nt or nt + 1 (nt + 2 would need xt = nt + 1
 // and an error >= 1), i.e. taps x0 and x0 + 1 are window elements t..t+3.
 // The C-ABI rejects wider levels for this kernel (include/raftcorr.h).
+// xa, xb: x' of taps -R and +R, which plan_pair has already evaluated for the
+// exact span.
 template <int R>
-__device__ __forceinline__ void window_taps(const float *w, float xl, float nwin, int W,
-                                            float *res) {
-    constexpr int T = 2 * R + 1;
-    const float Wm1 = (float)(W - 1), half = Wm1 / 2.0f;
-    const DivRN dv = div_prep(Wm1);
+__device__ __forceinline__ void window_taps(const float *w, float xl, float nwin, const LevelConsts &lc,
+                                            float xa, float xb, float *res) {
+    constexpr int T = 2 * R + 1, NW = 2 * R + 4;
+    // opaque copies: the selects must stay selects of registers (folded into
+    // a load from a select of addresses, the window goes to scratch memory:
+    // 112 B/lane and 87 instead of 14 vector loads per wave)
+    float e[NW];
+#pragma unroll
+    for (int j = 0; j < NW; ++j) {
+        e[j] = w[j];
+        asm("" : "+v"(e[j]));
+    }
 #pragma unroll
     for (int t = 0; t < T; ++t) {
-        const float xt = (float)(t - R) + xl;
-        const float xn = div_rn(2.0f * xt, dv) - 1.0f;
-        const float xp = (xn + 1.0f) * half;
+        const float xp = t == 0 ? xa : (t == T - 1 ? xb : tap_xp(xl, t - R, lc));
         const float x0 = floorf(xp);
         const float w1 = xp - x0, w0 = 1.0f - w1;
         const float nt = nwin + (float)(t - R);
         const bool lo_ = x0 < nt, hi_ = x0 > nt;
-        // opaque copies: the selects must stay selects of registers (folded
-        // into a load from a select of addresses, the window goes to scratch
-        // memory: 112 B/lane and 87 instead of 14 vector loads per wave)
-        float e0 = w[t], e1 = w[t + 1], e2 = w[t + 2], e3 = w[t + 3];
-        asm("" : "+v"(e0), "+v"(e1), "+v"(e2), "+v"(e3));
-        const float v0 = lo_ ? e0 : (hi_ ? e2 : e1);
-        const float v1 = lo_ ? e1 : (hi_ ? e3 : e2);
+        const float v0 = lo_ ? e[t] : (hi_ ? e[t + 2] : e[t + 1]);
+        const float v1 = lo_ ? e[t + 1] : (hi_ ? e[t + 3] : e[t + 2]);
         res[t] = fmaf(w1, v1, w0 * v0);
     }
 }
@@ -201,14 +247,11 @@ __device__ __forceinline__ float derived_elem_bf16(const uint16_t *row, long lon
 }
 
 template <int R, int S, bool BF16 = false>
-__device__ __forceinline__ void level_taps_mem(const void *rowv, float xl, int W, float *res) {
+__device__ __forceinline__ void level_taps_mem(const void *rowv, float xl, const LevelConsts &lc, float *res) {
     constexpr int T = 2 * R + 1;
-    const float Wm1 = (float)(W - 1), half = Wm1 / 2.0f;
-    const DivRN dv = div_prep(Wm1);
+    const float Wm1 = lc.Wm1;
     for (int t = 0; t < T; ++t) {
-        const float xt = (float)(t - R) + xl;
-        const float xn = div_rn(2.0f * xt, dv) - 1.0f;
-        const float xp = (xn + 1.0f) * half;
+        const float xp = tap_xp(xl, t - R, lc);
         const float x0 = floorf(xp);
         const float w1 = xp - x0, w0 = 1.0f - w1;
         const bool ok0 = (x0 >= 0.0f) && (x0 <= Wm1);
@@ -227,25 +270,37 @@ __device__ __forceinline__ void level_taps_mem(const void *rowv, float xl, int W
     }
 }
 
-template <int R, bool NOFALLBACK = false, bool BF16 = false, class Sink>
-__device__ __forceinline__ void finish_pair(const PairSpan<R, BF16> &ps, const LookupArgs &a, int lo,
-                                            float x, long long pp, Sink &&sink) {
+// The span's elements from its loaded chunks: span element j = chunk element
+// j + sh, sh in {0, 2, .., EPC-2}.  This consumes the chunks: after it their
+// registers are free for the next span's loads.
+template <int R, bool BF16>
+__device__ __forceinline__ void span_shift(const PairSpan<R, BF16> &ps, float *s) {
     typedef PairSpan<R, BF16> PS;
-    constexpr int T = 2 * R + 1, NW = PS::NW, NS = PS::NS, EPC = PS::EPC;
-    const int Wlo = a.W[lo], Whi = a.W[lo + 1];
-    // span element j = chunk element j + sh, sh in {0, 2, .., EPC-2}
-    float s[NS];
 #pragma unroll
-    for (int j = 0; j < NS; ++j) {
+    for (int j = 0; j < PS::NS; ++j) {
         float v = ps.elem(j);
 #pragma unroll
-        for (int d = 2; d < EPC; d += 2)
-            if (j + d < PS::NC * EPC) v = (ps.sh == d) ? ps.elem(j + d) : v;
+        for (int d = 2; d < PS::EPC; d += 2)
+            if (j + d < PS::NC * PS::EPC) v = (ps.sh == d) ? ps.elem(j + d) : v;
         s[j] = v;
     }
+}
+
+// Both levels of a pair from its span s[NS]: the two windows (after which
+// the span is dead), then the even level's taps and stores, then the odd
+// level's, so that one level's x' and results are live at a time.
+template <int R, bool NOFALLBACK = false, bool BF16 = false, class Sink, class Mid>
+__device__ __forceinline__ void finish_span(const PairSpan<R, BF16> &ps, const float *s, const LookupArgs &a,
+                                            int lo, float x, long long pp, Sink &&sink, Mid &&mid) {
+    typedef PairSpan<R, BF16> PS;
+    constexpr int T = 2 * R + 1, NW = PS::NW;
+    const int Wlo = a.W[lo], Whi = a.W[lo + 1];
     const int mi = (int)ps.m - R - 1, ni = (int)ps.n - R - 1;
     const int dd = (int)ps.n - 2 * (int)ps.m;
-    float wodd[NW], weven[NW];
+    const float xlo = x / (float)(1 << lo), xhi = x / (float)(2 << lo);
+    const bool mem = !NOFALLBACK && ps.inwin && !ps.valid;            // subnormal x only
+    const char *row = static_cast<const char *>(a.lvl[lo]) + pp * a.ld[lo] * PS::ES;
+    float weven[NW], wodd[NW];
 #pragma unroll
     for (int jj = 0; jj < NW; ++jj) {
         float pm = (s[2 * jj] + s[2 * jj + 1]) * 0.5f;      // model.py:294 in fp32
@@ -254,19 +309,25 @@ __device__ __forceinline__ void finish_pair(const PairSpan<R, BF16> &ps, const L
         const float e = dd == 0 ? s[R + 1 + jj] : s[R + 2 + jj];
         weven[jj] = (unsigned)(ni + jj) < (unsigned)Wlo ? e : 0.0f;
     }
-    const float xlo = x / (float)(1 << lo), xhi = x / (float)(2 << lo);
-    float r0[T], r1[T];
-    window_taps<R>(weven, xlo, ps.n, Wlo, r0);
-    window_taps<R>(wodd, xhi, ps.m, Whi, r1);
-    if (!NOFALLBACK && __builtin_expect(ps.inwin && !ps.valid, 0)) {   // subnormal x only
-        const char *row = static_cast<const char *>(a.lvl[lo]) + pp * a.ld[lo] * PS::ES;
-        level_taps_mem<R, 1, BF16>(row, xlo, Wlo, r0);
-        level_taps_mem<R, 2, BF16>(row, xhi, Whi, r1);
-    }
+    const LevelConsts clo = level_consts(a, lo), chi = level_consts(a, lo + 1);
+    float r[T];
+    window_taps<R>(weven, xlo, ps.n, clo, ps.xe[0], ps.xe[1], r);
+    if (__builtin_expect(mem, 0)) level_taps_mem<R, 1, BF16>(row, xlo, clo, r);
 #pragma unroll
-    for (int t = 0; t < T; ++t) sink(lo * T + t, r0[t]);
+    for (int t = 0; t < T; ++t) sink(lo * T + t, r[t]);
+    mid();
+    window_taps<R>(wodd, xhi, ps.m, chi, ps.xe[2], ps.xe[3], r);
+    if (__builtin_expect(mem, 0)) level_taps_mem<R, 2, BF16>(row, xhi, chi, r);
 #pragma unroll
-    for (int t = 0; t < T; ++t) sink((lo + 1) * T + t, r1[t]);
+    for (int t = 0; t < T; ++t) sink((lo + 1) * T + t, r[t]);
+}
+
+template <int R, bool NOFALLBACK = false, bool BF16 = false, class Sink>
+__device__ __forceinline__ void finish_pair(const PairSpan<R, BF16> &ps, const LookupArgs &a, int lo,
+                                            float x, long long pp, Sink &&sink) {
+    float s[PairSpan<R, BF16>::NS];
+    span_shift<R, BF16>(ps, s);
+    finish_span<R, NOFALLBACK, BF16>(ps, s, a, lo, x, pp, sink, [] {});
 }
 
 // One lane's pixel of one group: index, x, output offset (elements of a.out,
@@ -296,8 +357,16 @@ __device__ __forceinline__ PairPixel pair_pixel(const LookupArgs &a, long long p
 }
 
 // NL = 2 (levels 0-1) or 4 (levels 0-3; level 2 stored, levels 1 and 3 derived).
-// Both spans' loads issue first; pair 0's math and stores run while pair 2's
-// loads are in flight.  Measured and not kept: 16-B output
+// Load schedule (pinned with sched_barrier): span 0's 7
+// loads; span 2's address math while they are in flight; span 0's chunks
+// shifted into its span; level 0's taps and stores; span 2's 7 loads, into
+// the registers span 0's chunks held; level 1's taps and stores while those
+// are in flight; then levels 2 and 3.  A wave makes two round trips of 7
+// loads, not one of 14: with all 14 issued first (or span 2's right after
+// the shift) the kernel needs 140-144 VGPRs, three waves per SIMD instead of
+// four, and is slower (25.0 / 25.2 us against 22.7).  Left to the compiler,
+// span 2's loads sank below both levels of span 0 (24.0 us).
+// Measured and not kept: 16-B output
 // stores through a per-wave LDS tile (9 instead of 36 store instructions per
 // wave: 26.0 vs 25.8 us), two pixels per lane with both pixels' loads in
 // flight (26.6 us, 198 VGPRs).
@@ -322,9 +391,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     const PairPixel q = pair_pixel<R, NL>(a, (long long)blk * 256);
     OT *const outp = reinterpret_cast<OT *>(a.out) + q.ooff;
     PairSpan<R, BF16> sp[NP];
-#pragma unroll
-    for (int k = 0; k < NP; ++k)
-        issue_pair<R, BF16>(sp[k], a, 2 * k, q.x, q.pblk, q.lrow);
+    // The load schedule, pinned: the first span's loads go
+    // out before the second span's address math; the second span's loads go
+    // out between the two levels of the first (see below).
+    PairLoads<R, BF16> pl[NP];
+    pl[0] = plan_pair_loads<R, BF16>(sp[0], a, 0, q.x, q.pblk, q.lrow);
+    load_pair<R, BF16>(sp[0], pl[0]);
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (NP > 1) pl[1] = plan_pair_loads<R, BF16>(sp[1], a, 2, q.x, q.pblk, q.lrow);
     constexpr int C = NL * (2 * R + 1);
     // CL: channels-last output (RC_OUT_CHANNELS_LAST), out[p*C + ch].  A
     // wave's 64 pixels own one contiguous run of 64*C elements; it is gathered
@@ -342,7 +416,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
         }
     };
 #pragma unroll
-    for (int k = 0; k < NP; ++k) finish_pair<R, M == 2, BF16>(sp[k], a, 2 * k, q.x, q.pp, sink);
+    for (int k = 0; k < NP; ++k) {
+        float s[PairSpan<R, BF16>::NS];
+        span_shift<R, BF16>(sp[k], s);
+        // The next span's loads: after this span's even level is done and
+        // stored, before its odd level.  By then the shift has consumed this
+        // span's chunks and the even level's window and x' are dead, so the
+        // 28 registers the loads land in fit under 128 VGPRs (4 waves per
+        // SIMD: the one-round grid); right after the shift they do not (140).
+        // The scheduler may move nothing across the barriers.
+        auto next = [&] {
+            if constexpr (NP > 1) {
+                if (k == 0) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    load_pair<R, BF16>(sp[1], pl[1]);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        };
+        finish_span<R, M == 2, BF16>(sp[k], s, a, 2 * k, q.x, q.pp, sink, next);
+        __builtin_amdgcn_sched_barrier(0);
+    }
     if constexpr (TILE) {
         // the wave's tile is private and LDS runs a wave's operations in
         // order: no barrier.  The run starts 64*C*sizeof(OT)-byte aligned.
@@ -384,14 +478,11 @@ __device__ __forceinline__ void sheared_taps_mem(const LookupArgs &a, int lo, fl
     auto elem = [&](long long j) { return S[(base - j) * a.ld[lo] + w1]; };
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
-        const int W = a.W[lo + half];
-        const float Wm1 = (float)(W - 1), hw = Wm1 / 2.0f;
-        const DivRN dv = div_prep(Wm1);
+        const LevelConsts lc = level_consts(a, lo + half);
+        const float Wm1 = lc.Wm1;
         const float xl = x / (float)(1 << (lo + half));
         for (int t = 0; t < T; ++t) {
-            const float xt = (float)(t - R) + xl;
-            const float xn = div_rn(2.0f * xt, dv) - 1.0f;
-            const float xp = (xn + 1.0f) * hw;
+            const float xp = tap_xp(xl, t - R, lc);
             const float x0 = floorf(xp);
             const float wt1 = xp - x0, wt0 = 1.0f - wt1;
             const bool ok0 = (x0 >= 0.0f) && (x0 <= Wm1);
@@ -444,21 +535,9 @@ __global__ __launch_bounds__(256) void lookup_sheared_pair_kernel(LookupArgs a) 
     for (int k = 0; k < NP; ++k) {
         const int lo = 2 * k;
         PairSpan<R> &ps = sp[k];
-        const int Wlo = a.W[lo], Whi = a.W[lo + 1];
-        const float xlo = x / (float)(1 << lo), xhi = x / (float)(2 << lo);
-        ps.inwin = (xhi > -(float)(R + 4)) && (xhi < (float)(Whi + R + 4));
-        ps.m = ps.inwin ? floorf(xhi) : 0.0f;
-        ps.n = ps.inwin ? floorf(xlo) : 0.0f;
-        const int dd = (int)ps.n - 2 * (int)ps.m;
-        ps.valid = ps.inwin && (dd == 0 || dd == 1);
-        int lo_e = 0x7FFFFFFF, hi_e = -1;
-        if (ps.inwin) {
-            int f, l;
-            tap_span<R>(xlo, Wlo, f, l);
-            if (f <= l) { lo_e = f; hi_e = l; }
-            tap_span<R>(xhi, Whi, f, l);
-            if (f <= l) { lo_e = min(lo_e, 2 * f); hi_e = max(hi_e, 2 * l + 1); }
-        }
+        const int Wlo = a.W[lo];
+        int lo_e, hi_e;
+        plan_pair<R, false>(ps, a, lo, x, lo_e, hi_e);
         ps.sh = 0;
         const int sa = 2 * ((int)ps.m - R - 1);
         const long long K = a.shk[lo], ldw = a.ld[lo];
@@ -495,32 +574,19 @@ __global__ __launch_bounds__(256) void lookup_sheared_pair_kernel(LookupArgs a) 
 // 2(floor(m1/4) - R - 1)) in record r: ONE 128-B line per pixel instead of
 // two.  A pixel outside the records' m1 range takes the
 // nearest record; its exact spans are then empty or lie at the row edge that
-// record covers.  The chunks are read with issue_pair's exact-span predicate
+// record covers.  The chunks are read with plan_pair's exact-span predicate
 // and finish_pair runs unchanged, so the output is the row layout's bit for
 // bit.
 
-// issue_pair over a record: level-lo element e sits in slot e - e_first + slot_first.
+// plan_pair_loads / load_pair over a record: level-lo element e sits in slot e - e_first + slot_first.
 // plan_record_pair fills the span's window fields and returns the first
 // chunk's slot (cb, a multiple of 8) and which of the NC chunks the taps read.
 template <int R>
 __device__ __forceinline__ int plan_record_pair(PairSpan<R, true> &ps, const LookupArgs &a, int lo, float x,
                                                 int e_first, int slot_first, uint32_t &okmask) {
     typedef PairSpan<R, true> PS;
-    const int Wlo = a.W[lo], Whi = a.W[lo + 1];
-    const float xlo = x / (float)(1 << lo), xhi = x / (float)(2 << lo);
-    ps.inwin = (xhi > -(float)(R + 4)) && (xhi < (float)(Whi + R + 4));
-    ps.m = ps.inwin ? floorf(xhi) : 0.0f;
-    ps.n = ps.inwin ? floorf(xlo) : 0.0f;
-    const int dd = (int)ps.n - 2 * (int)ps.m;
-    ps.valid = ps.inwin && (dd == 0 || dd == 1);
-    int lo_e = 0x7FFFFFFF, hi_e = -1;
-    if (ps.inwin) {
-        int f, l;
-        tap_span<R>(xlo, Wlo, f, l);
-        if (f <= l) { lo_e = f; hi_e = l; }
-        tap_span<R>(xhi, Whi, f, l);
-        if (f <= l) { lo_e = min(lo_e, 2 * f); hi_e = max(hi_e, 2 * l + 1); }
-    }
+    int lo_e, hi_e;
+    plan_pair<R, true>(ps, a, lo, x, lo_e, hi_e);
     const int sslot = 2 * ((int)ps.m - R - 1) - e_first + slot_first;   // span start (even)
     const int cb = sslot >= 0 ? sslot & ~7 : -((-sslot + 7) & ~7);      // chunk base (floor to 8)
     ps.sh = sslot - cb;
@@ -594,14 +660,11 @@ __device__ __forceinline__ void record_taps_mem(const LookupArgs &a, const uint1
     };
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
-        const int W = a.W[lo + half];
-        const float Wm1 = (float)(W - 1), hw = Wm1 / 2.0f;
-        const DivRN dv = div_prep(Wm1);
+        const LevelConsts lc = level_consts(a, lo + half);
+        const float Wm1 = lc.Wm1;
         const float xl = x / (float)(1 << (lo + half));
         for (int t = 0; t < T; ++t) {
-            const float xt = (float)(t - R) + xl;
-            const float xn = div_rn(2.0f * xt, dv) - 1.0f;
-            const float xp = (xn + 1.0f) * hw;
+            const float xp = tap_xp(xl, t - R, lc);
             const float x0 = floorf(xp);
             const float wt1 = xp - x0, wt0 = 1.0f - wt1;
             const bool ok0 = (x0 >= 0.0f) && (x0 <= Wm1);

@@ -15,6 +15,12 @@ distributions that differ only in locality:
           weights, default args) on a 540x960 textured pair whose right image
           is the left one shifted by 16 px: the field the update block feeds the
           lookup (smooth, with the network's own structure).
+  integer x = w1 exactly (coords_grid): the network's first iteration, where
+          the round trip moves many taps' floors (tests/test_lookup_taps_host.py).
+With --libs name=path,... whole builds of libraftcorr.so (say, the parent
+commit's and this tree's) are checked bit for bit against the first one and
+timed on the fields of --dev-fields, one 32-launch sequence per library per
+round, interleaved (how DESIGN.md §3.2d's round-8 table was measured).
 With --dev-variants the listed RAFTCORR_LOOKUP_VARIANT values (dev library)
 are checked bit for bit against the product kernel and timed on the fields of
 --dev-fields (default: bench).
@@ -51,6 +57,8 @@ def coords_sets(B, H, W1, W2, n, kind, dev):
             h = torch.arange(H).float().view(1, H, 1)
             d = 32 + 24 * torch.sin(w / 17.0 + ph) * torch.cos(h / 13.0 + ph)
             c[:, 0] -= d + 0.37
+        elif kind == "integer":
+            pass
         elif kind == "net":
             return net_coords(B, H, W1, n, dev)
         out.append(c.to(dev))
@@ -107,6 +115,8 @@ def main():
                          "(libraftcorr_dev.so)")
     ap.add_argument("--dev-fields", default="bench",
                     help="coordinate fields the dev variants are timed on (comma list)")
+    ap.add_argument("--libs", default="",
+                    help="name=path,...: builds of libraftcorr.so to A/B (first = reference)")
     ap.add_argument("--only-dev", action="store_true",
                     help="time only the dev variants, default kernel only")
     a = ap.parse_args()
@@ -120,7 +130,32 @@ def main():
     with torch.no_grad():
         blk = CorrBlock1D(f1, f2, num_levels=L, radius=r)
         pyr = blk.corr_pyramid
-        for kind in (() if a.only_dev else ("bench", "same", "row", "smooth", "net")):
+        if a.libs:
+            from raft_stereo_amd import _lib
+            libs = [x.split("=", 1) for x in a.libs.split(",")]
+            dll = {n: _lib._open(p) for n, p in libs}
+            for kind in a.dev_fields.split(","):
+                cs = coords_sets(B, H, W1, W2, iters, kind, dev)
+                ref_out, per = None, {n: [] for n, _ in libs}
+                try:
+                    for n, _ in libs:
+                        _lib._active = dll[n]
+                        o = blk(cs[0])
+                        torch.cuda.synchronize()
+                        ref_out = o.clone() if ref_out is None else ref_out
+                        res[f"{kind}/{n}/bit_identical"] = bool(torch.equal(
+                            torch.nan_to_num(o, nan=7.25), torch.nan_to_num(ref_out, nan=7.25)))
+                    for _ in range(a.reps):
+                        for n, _ in libs:
+                            _lib._active = dll[n]
+                            per[n].append(time_seq(blk, cs, 1))
+                finally:
+                    _lib._active = None
+                for n, _ in libs:
+                    v = sorted(per[n])
+                    res[f"{kind}/{n}/us"] = {"median": round(v[len(v) // 2], 2), "min": round(v[0], 2),
+                                             "max": round(v[-1], 2)}
+        for kind in (() if a.only_dev or a.libs else ("bench", "same", "row", "smooth", "net")):
             cs = coords_sets(B, H, W1, W2, iters, kind, dev)
             l1 = pyr[:2] + [None] * (L - 2)
             for name, fn in (("default", blk), ("chain_l1", lambda c: rcorr.lookup_chain(l1, c, L, r)),
