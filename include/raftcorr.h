@@ -14,6 +14,11 @@
  *   rc_corr_lookup_conv_backward  its gradient with respect to the
  *                   correlation, the conv weight and the bias, for training
  *                   with the fused layer (the lookup is recomputed).
+ *   rc_corr_lookup_chain_conv, rc_corr_lookup_chain_conv_backward  the same
+ *                   fused layer and its gradient on the PAIR layout (levels
+ *                   0 and 2 stored, 1 and 3 derived in registers), with an
+ *                   fp32, fp16 or bf16 output: what CorrBlock1D stores by
+ *                   default, so nothing is pooled for the fused path.
  *   rc_corr_lookup_chain rc_corr_lookup for a pool-chain fp32 pyramid,
  *                   reading levels 0-1 only (the default of CorrBlock1D).
  *   rc_corr_lookup_step  coords update + flow + lookup of one loop
@@ -43,6 +48,10 @@
 extern "C" {
 #endif
 
+/* Version 13 also covers rc_corr_lookup_chain_conv and
+ * rc_corr_lookup_chain_conv_backward: they were added without changing any
+ * existing entry point, flag or layout (purely additive), so the number did
+ * not move.  A caller that needs them checks for the symbols. */
 #define RC_ABI_VERSION 13
 
 /* element types */
@@ -208,7 +217,9 @@ int rc_corr_lookup(const void *const *pyr, const int *widths, const long *pyr_ld
  *   corr = the rc_corr_lookup result (k = level*(2r+1) + tap, never written),
  *   weight: [cout][levels*(2r+1)] fp32 (a 1x1 Conv2d weight), bias: [cout] or
  *   NULL, act = ReLU when relu != 0.  out: [B][cout][H][W1] fp32.
- *   levels 2..4, radius 1..4. */
+ *   levels 2..4, radius 1..4.  Reads every level (one window each): for the
+ *   pair layout CorrBlock1D stores, and for an fp16 / bf16 output, see
+ *   rc_corr_lookup_chain_conv. */
 int rc_corr_lookup_conv(const void *const *pyr, const int *widths, const long *pyr_ld,
                         int pyr_dtype, int levels, int radius, const float *coords_x,
                         long coord_batch_stride, int B, int H, int W1,
@@ -245,6 +256,52 @@ int rc_corr_lookup_conv_backward(const void *const *pyr, const int *widths, cons
                                  const float *weight, const float *bias, int cout, int relu,
                                  const float *grad_out, float *grad_corr, float *grad_weight,
                                  float *grad_bias, float *workspace, void *stream);
+
+/* rc_corr_lookup_conv on the pair layout (added within ABI v13): the lookup
+ * half is rc_corr_lookup_chain's pair kernel -- levels 0 and 2 read (each
+ * pixel's span from the RC_SHADOW copy that touches fewer lines, where
+ * given), levels 1 and 3 derived in registers -- and the conv half is
+ * rc_corr_lookup_conv's chain (bias, one fmaf per k ascending, ReLU), so with
+ * an fp32 `out` the result equals rc_corr_lookup_conv's on the full pyramid
+ * bit for bit, at ~2.8 instead of ~4.4 128-B lines read per pixel and with
+ * levels 1 and 3 never in memory.
+ *   Layout: pair only -- levels == 2, or levels == 4 with pyr[2] != NULL;
+ *   pyr[1] and pyr[3] may be NULL and are never read.  RC_F32 or RC_BF16,
+ *   RC_SHADOW / RC_SHADOW_LEVEL(l) honoured as by the pair kernel.  Checks
+ *   are rc_corr_lookup_chain's (widths[i] == widths[i-1] / 2, level-0 width
+ *   <= 65536, radius 1..4, 16-byte aligned levels, row strides whole 16-B
+ *   chunks).
+ *   out: [B][cout][H][W1] fp32, or IEEE fp16 / bfloat16 with RC_OUT_F16 /
+ *   RC_OUT_BF16: each element the fp32 result rounded once to nearest even
+ *   (Tensor.to(dtype) of the fp32 output bit for bit; conventions as for
+ *   rc_corr_lookup_chain).  Both flags: RC_EINVAL.
+ *   RC_EUNSUPPORTED, with a message, before any launch and whatever B is:
+ *   RC_OUT_CHANNELS_LAST, RC_LAYOUT_RECORDS, RC_LAYOUT_DISPARITY, 3 levels,
+ *   4 levels without level 2.  cout < 1 and a null weight (with B*H*W1 > 0)
+ *   are RC_EINVAL; B*H*W1 == 0 is RC_OK. */
+int rc_corr_lookup_chain_conv(const void *const *pyr, const int *widths, const long *pyr_ld,
+                              int pyr_dtype, int levels, int radius, const float *coords_x,
+                              long coord_batch_stride, int B, int H, int W1,
+                              const float *weight, const float *bias, int cout, int relu,
+                              void *out, void *stream);
+
+/* Backward of rc_corr_lookup_chain_conv (added within ABI v13):
+ * rc_corr_lookup_conv_backward with the correlation recomputed from the pair
+ * layout.  Arguments, NULL combinations, workspace
+ * (RC_LOOKUP_CONV_BWD_WS, the same layout; the second launch is the same
+ * reduction) and the B*H*W1 == 0 behaviour are rc_corr_lookup_conv_backward's;
+ * layout, checks and refusals are rc_corr_lookup_chain_conv's.  grad_out and
+ * the three gradients are fp32: RC_OUT_F16 / RC_OUT_BF16 are RC_EUNSUPPORTED
+ * (a half-precision forward output is the rounded fp32 one; widen its
+ * gradient).  With the same correlation bits, the same 256 pixels per
+ * workgroup and the same summation order, all three gradients equal
+ * rc_corr_lookup_conv_backward's on the full pyramid bit for bit. */
+int rc_corr_lookup_chain_conv_backward(const void *const *pyr, const int *widths, const long *pyr_ld,
+                                       int pyr_dtype, int levels, int radius, const float *coords_x,
+                                       long coord_batch_stride, int B, int H, int W1,
+                                       const float *weight, const float *bias, int cout, int relu,
+                                       const float *grad_out, float *grad_corr, float *grad_weight,
+                                       float *grad_bias, float *workspace, void *stream);
 
 /* Lookup over a pool-chain fp32 pyramid (what rc_corr_build writes), same
  * arguments and bit-identical results as rc_corr_lookup with RC_F32, but

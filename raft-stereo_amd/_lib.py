@@ -24,7 +24,7 @@ RC_BUILD_EXACT_F32 = 0x20000     # rc_corr_build flag: exact fp32 MFMA kernel in
 RC_GRAD_OVERWRITE = 0x40000      # rc_corr_lookup_backward_calls flag: write the sum, do not add
 RC_LAYOUT_DISPARITY = 0x80000    # rc_corr_build / rc_corr_lookup_chain: disparity-major levels 0, 2 (ABI v9)
 RC_LAYOUT_RECORDS = 0x100000     # rc_corr_build / _lookup_chain / _lookup_step: bf16 levels 0, 2 as records (ABI v10)
-RC_OUT_F16 = 0x40000             # rc_corr_lookup_chain / _lookup_step: fp16 output (pair / records kernel, ABI v13)
+RC_OUT_F16 = 0x40000             # rc_corr_lookup_chain / _lookup_step / _lookup_chain_conv: fp16 output (ABI v13)
 RC_OUT_BF16 = 0x200000           # ... bf16 output
 RC_REC_SLOTS, RC_REC_BYTES = 64, 128
 
@@ -68,6 +68,11 @@ SIGNATURES = {
     "rc_corr_lookup_conv_backward": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_l), _i,
                                           _i, _i, _vp, _l, _i, _i, _i, _vp, _vp, _i, _i,
                                           _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rc_corr_lookup_chain_conv": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_l), _i,
+                                       _i, _i, _vp, _l, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "rc_corr_lookup_chain_conv_backward": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_l),
+                                                _i, _i, _i, _vp, _l, _i, _i, _i, _vp, _vp, _i, _i,
+                                                _vp, _vp, _vp, _vp, _vp, _vp]),
     "rc_corr_lookup_chain": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_l), _i,
                                   _i, _i, _vp, _l, _i, _i, _i, _vp, _vp]),
     "rc_corr_lookup_step": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_i), ctypes.POINTER(_l), _i,
@@ -99,7 +104,13 @@ def _open(path):
             "`python -c 'import __graft_entry__ as g; g.build()'`")
     dll = ctypes.CDLL(path)
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(dll, name)
+        try:
+            fn = getattr(dll, name)
+        except AttributeError:
+            # entry points are added within an ABI version (additive): a
+            # library built before one of them must not be used
+            raise CorrLibError(f"raft_stereo_amd: {path} has no symbol {name} (built from older "
+                               "sources); rebuild the library") from None
         fn.restype = res
         fn.argtypes = args
     if dll.rc_abi_version() != ABI_VERSION:

@@ -251,28 +251,33 @@ def _level_args(pyramid, num_levels):
             _lib.long_array([_row_stride(t) for t in levels]), _dtype_code(levels[0].dtype))
 
 
-def lookup_convc1(pyramid, coords, num_levels, radius, weight, bias=None, relu=True):
-    """Lookup fused with a 1x1 conv (+ReLU): relu(conv1x1(lookup(coords))),
-    i.e. BasicMotionEncoder's ``F.relu(self.convc1(corr))`` (model.py:199, :206)."""
-    x, cbs = _check_coords(pyramid, coords)
-    B, _, H, W1 = coords.shape
-    cin = num_levels * (2 * radius + 1)
+def _convc1_params(coords, cin, weight, bias):
+    """convc1's weight as (cout, cin) fp32 and its bias as (cout,) fp32 or None."""
     _require_hip(weight, "weight")
     if weight.device != coords.device:
         raise RuntimeError("lookup_convc1: weight and coords on different devices")
     w = weight.detach().reshape(weight.shape[0], -1).float().contiguous()
     if w.shape[1] != cin:
         raise RuntimeError(f"lookup_convc1: weight has {w.shape[1]} input channels, lookup gives {cin}")
-    cout = w.shape[0]
     b = None
     if bias is not None:
         _require_hip(bias, "bias")
         if bias.device != coords.device:
             raise RuntimeError("lookup_convc1: bias and coords on different devices")
-        if bias.numel() != cout:
-            raise RuntimeError(f"lookup_convc1: bias has {bias.numel()} elements, weight has {cout} "
+        if bias.numel() != w.shape[0]:
+            raise RuntimeError(f"lookup_convc1: bias has {bias.numel()} elements, weight has {w.shape[0]} "
                                "output channels")
         b = bias.detach().float().contiguous()
+    return w, b
+
+
+def lookup_convc1(pyramid, coords, num_levels, radius, weight, bias=None, relu=True):
+    """Lookup fused with a 1x1 conv (+ReLU): relu(conv1x1(lookup(coords))),
+    i.e. BasicMotionEncoder's ``F.relu(self.convc1(corr))`` (model.py:199, :206)."""
+    x, cbs = _check_coords(pyramid, coords)
+    B, _, H, W1 = coords.shape
+    w, b = _convc1_params(coords, num_levels * (2 * radius + 1), weight, bias)
+    cout = w.shape[0]
     out = torch.empty((B, cout, H, W1), dtype=torch.float32, device=coords.device)
     if B * H * W1 == 0:
         return out
@@ -410,6 +415,76 @@ def lookup_chain(pyramid, coords, num_levels, radius, shadow=False, channels_las
     if channels_last and not cl:
         out = out.contiguous(memory_format=torch.channels_last)
     return out if od is None else out.to(od)     # no copy where the kernel wrote od
+
+
+def lookup_chain_convc1(pyramid, coords, num_levels, radius, weight, bias=None, relu=True, shadow=False,
+                        out_dtype=None):
+    """rc_corr_lookup_chain_conv: :func:`lookup_convc1` on the pair layout --
+    ``pyramid`` holds levels 0 and (with 4 levels) 2, the other entries may be
+    None and are never read; ``shadow`` as for :func:`lookup_chain`.  The fp32
+    result equals :func:`lookup_convc1` on the full pool-chain pyramid bit for
+    bit.  ``out_dtype`` (torch.float16 / torch.bfloat16): the kernel writes
+    the output in that dtype, ``fp32_result.to(out_dtype)`` bit for bit."""
+    od = _check_out_dtype(out_dtype)
+    x, cbs = _check_coords(pyramid, coords)
+    B, _, H, W1 = coords.shape
+    if not _pair_layout(pyramid, num_levels):
+        raise _lib.CorrLibError("lookup_chain_convc1: the pair layout only (2 levels, or 4 levels with "
+                                "level 2 present); lookup_convc1 reads a full pyramid")
+    w, b = _convc1_params(coords, num_levels * (2 * radius + 1), weight, bias)
+    cout = w.shape[0]
+    out = torch.empty((B, cout, H, W1), dtype=torch.float32 if od is None else od, device=coords.device)
+    if B * H * W1 == 0:
+        return out
+    keep, ptrs, widths, lds, dt = _chain_args(pyramid, num_levels, shadow)
+    with torch.cuda.device(coords.device):
+        rc = _lib.lib().rc_corr_lookup_chain_conv(
+            ptrs, widths, lds, dt | _out_flag(od), num_levels, radius, x.data_ptr(), cbs, B, H, W1,
+            w.data_ptr(), b.data_ptr() if b is not None else None, cout, int(relu),
+            out.data_ptr(), _stream(coords.device))
+    _lib.check(rc, "rc_corr_lookup_chain_conv")
+    return out
+
+
+def lookup_chain_convc1_backward(pyramid, coords, num_levels, radius, weight, bias, relu, grad_out,
+                                 need_corr=True, need_weight=True, need_bias=True, shadow=False):
+    """rc_corr_lookup_chain_conv_backward: :func:`lookup_convc1_backward` with
+    the lookup recomputed from the pair layout (``pyramid`` / ``shadow`` as
+    for :func:`lookup_chain_convc1`).  Same arguments and results -- bit for
+    bit those of :func:`lookup_convc1_backward` on the full pyramid."""
+    x, cbs = _check_coords(pyramid, coords)
+    B, _, H, W1 = coords.shape
+    cin = num_levels * (2 * radius + 1)
+    dev = coords.device
+    if not _pair_layout(pyramid, num_levels):
+        raise _lib.CorrLibError("lookup_chain_convc1_backward: the pair layout only (2 levels, or 4 levels "
+                                "with level 2 present)")
+    w, b = _convc1_params(coords, cin, weight, bias)
+    cout = w.shape[0]
+    if tuple(grad_out.shape) != (B, cout, H, W1):
+        raise RuntimeError(f"lookup_convc1: grad_out {tuple(grad_out.shape)} != {(B, cout, H, W1)}")
+    if not (need_corr or need_weight or need_bias):
+        return None, None, None
+    g = grad_out.detach().float().contiguous()
+    P = B * H * W1
+    gc = torch.empty((B, cin, H, W1), dtype=torch.float32, device=dev) if need_corr else None
+    gw = torch.empty((cout, cin), dtype=torch.float32, device=dev) if need_weight else None
+    gb = torch.empty((cout,), dtype=torch.float32, device=dev) if need_bias else None
+    if P == 0:
+        for t in (gw, gb):
+            if t is not None:
+                t.zero_()
+        return gc, gw, gb
+    ws = (torch.empty(_lib.lookup_conv_bwd_ws(P, cout, cin), dtype=torch.float32, device=dev)
+          if need_weight or need_bias else None)
+    keep, ptrs, widths, lds, dt = _chain_args(pyramid, num_levels, shadow)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().rc_corr_lookup_chain_conv_backward(
+            ptrs, widths, lds, dt, num_levels, radius, x.data_ptr(), cbs, B, H, W1,
+            w.data_ptr(), b.data_ptr() if b is not None else None, cout, int(relu), g.data_ptr(),
+            *(t.data_ptr() if t is not None else None for t in (gc, gw, gb, ws)), _stream(dev))
+    _lib.check(rc, "rc_corr_lookup_chain_conv_backward")
+    return gc, gw, gb
 
 
 # ------------------------------------------------- disparity-major layout
@@ -935,17 +1010,27 @@ class _LookupFn(torch.autograd.Function):
 class _LookupConvFn(torch.autograd.Function):
     """Autograd node of the differentiable fused lookup + convc1.  Saves
     coords, weight and bias only: the backward recomputes the lookup
-    (rc_corr_lookup_conv_backward), so the correlation tensor is kept neither
-    by the forward nor for the backward.  Like _LookupFn it consumes the
-    block's token (None when the fmaps need no gradient) and hands its
-    grad_corr to the shared _GradState."""
+    (rc_corr_lookup_conv_backward, or rc_corr_lookup_chain_conv_backward when
+    the pair kernels served the forward: ``shadow`` is not None then and
+    ``levels`` are the block's stored levels as they are), so the correlation
+    tensor is kept neither by the forward nor for the backward.  Like
+    _LookupFn it consumes the block's token (None when the fmaps need no
+    gradient) and hands its grad_corr to the shared _GradState.
+    ``out_dtype`` (fp16 / bf16): the node is ``fused_fp32(...).to(out_dtype)``
+    -- the incoming gradient is widened to fp32 and the ReLU mask is the fp32
+    ``pre > 0``."""
 
     @staticmethod
-    def forward(ctx, token, coords, weight, bias, state, levels, num_levels, radius, relu):
+    def forward(ctx, token, coords, weight, bias, state, levels, num_levels, radius, relu, shadow=None,
+                out_dtype=None):
         ctx.state = state if token is not None else None
-        ctx.levels, ctx.cfg = levels, (num_levels, radius, relu)
+        ctx.levels, ctx.cfg, ctx.shadow = levels, (num_levels, radius, relu), shadow
         ctx.save_for_backward(coords, weight, bias)
-        return lookup_convc1(levels, coords, num_levels, radius, weight, bias, relu)
+        if shadow is not None:
+            return lookup_chain_convc1(levels, coords, num_levels, radius, weight, bias, relu, shadow,
+                                       out_dtype)
+        out = lookup_convc1(levels, coords, num_levels, radius, weight, bias, relu)
+        return out if out_dtype is None else out.to(out_dtype)
 
     @staticmethod
     @once_differentiable
@@ -955,14 +1040,19 @@ class _LookupConvFn(torch.autograd.Function):
         need_corr = ctx.state is not None
         need_w = ctx.needs_input_grad[2]
         need_b = bias is not None and ctx.needs_input_grad[3]
-        gc, gw, gb = lookup_convc1_backward(ctx.levels, coords, num_levels, radius, weight, bias, relu,
-                                            grad_out, need_corr, need_w, need_b)
+        if ctx.shadow is not None:
+            gc, gw, gb = lookup_chain_convc1_backward(ctx.levels, coords, num_levels, radius, weight, bias,
+                                                      relu, grad_out.float(), need_corr, need_w, need_b,
+                                                      shadow=ctx.shadow)
+        else:
+            gc, gw, gb = lookup_convc1_backward(ctx.levels, coords, num_levels, radius, weight, bias, relu,
+                                                grad_out.float(), need_corr, need_w, need_b)
         token_grad = None
         if need_corr:
             ctx.state.accumulate(coords, gc)
             token_grad = ctx.state.token_grad(coords.device)
         return (token_grad, None, gw.view(weight.shape).to(weight.dtype) if need_w else None,
-                gb.view(bias.shape).to(bias.dtype) if need_b else None, None, None, None, None, None)
+                gb.view(bias.shape).to(bias.dtype) if need_b else None) + (None,) * 7
 
 
 class CorrBlock1D:
@@ -1298,20 +1388,39 @@ class CorrBlock1D:
             corr = corr.contiguous(memory_format=torch.channels_last)
         return (corr if od is None else corr.to(od)), new, flow
 
-    def lookup_convc1(self, coords, weight, bias=None, relu=True, differentiable=False):
+    def lookup_convc1(self, coords, weight, bias=None, relu=True, differentiable=False, out_dtype=None):
         """``relu(convc1(self(coords)))`` in one launch:
         the motion encoder's first layer (model.py:199, :206) fused into the
         lookup, so the (B, L(2r+1), H, W1) correlation never reaches HBM.
-        ``out_dtype`` does not apply: no correlation is written, and the
-        result is convc1's fp32 output.
+
+        ``out_dtype``: None / torch.float32 is convc1's fp32 output;
+        torch.float16 / torch.bfloat16 gives that result rounded to nearest
+        even, ``fused_fp32.to(out_dtype)`` bit for bit -- what a
+        mixed-precision ``convc2`` would cast it to.  The block's own
+        ``out_dtype`` does not apply here (no correlation is written): the
+        keyword decides, and without it the result is fp32 as ever.
+
+        Where the pair kernel serves the block's plain lookup (2 or 4 levels
+        in rows, the default), the fused pair kernels read the stored levels
+        0 and 2 as they are, shadow copies included, and derive levels 1 and
+        3 in registers (rc_corr_lookup_chain_conv): no level
+        is pooled into memory -- ``levels_stored`` is the same before and
+        after, forward and backward -- and the kernel writes ``out_dtype``
+        itself.  A 3-level, ``low_latency`` or replaced-``corr_pyramid``
+        block keeps the per-level kernel on levels 0 .. L-1 (pooled on first
+        use), with the cast after it.  Bit-identical results either way.
 
         ``differentiable=False`` is inference-only and raises when gradients
         are being recorded.  ``differentiable=True`` records an autograd node
         (first order only) when grad is enabled: its backward recomputes the
-        lookup (rc_corr_lookup_conv_backward), returns the
-        gradients of ``weight`` and ``bias`` and feeds the block's level
-        gradients like a plain ``self(coords)`` call, so the correlation
-        tensor is stored neither by the forward nor for the backward."""
+        lookup (rc_corr_lookup_conv_backward or its pair-layout twin,
+        DESIGN.md §3.2b), returns the gradients of ``weight`` and ``bias``
+        and feeds the block's level gradients like a plain ``self(coords)``
+        call, so the correlation tensor is stored neither by the forward nor
+        for the backward.  With a half-precision ``out_dtype`` the node is
+        the fp32 fused result followed by the cast: the incoming gradient is
+        widened to fp32."""
+        od = _check_out_dtype(out_dtype)
         grad = torch.is_grad_enabled()
         if not differentiable and grad and (self._token is not None or weight.requires_grad):
             raise RuntimeError("CorrBlock1D.lookup_convc1 is inference-only; use "
@@ -1319,11 +1428,19 @@ class CorrBlock1D:
                                "differentiable=True")
         if self._sheared is not None or self._records is not None:
             raise RuntimeError(f"CorrBlock1D.lookup_convc1: not available with layout={self.layout!r}")
+        L, r = self.num_levels, self.radius
+        if self._chain and _pair_layout(self._levels, L):
+            # the stored levels as they are (None = derived in registers)
+            if differentiable and grad:
+                return _LookupConvFn.apply(self._token, coords.detach(), weight, bias, self._state,
+                                           self._levels, L, r, bool(relu), self._shadow, od)
+            return lookup_chain_convc1(self._levels, coords, L, r, weight, bias, relu, self._shadow, od)
         levels = self._read_levels()
         if differentiable and grad:
             return _LookupConvFn.apply(self._token, coords.detach(), weight, bias, self._state, levels,
-                                       self.num_levels, self.radius, bool(relu))
-        return lookup_convc1(levels, coords, self.num_levels, self.radius, weight, bias, relu)
+                                       L, r, bool(relu), None, od)
+        out = lookup_convc1(levels, coords, L, r, weight, bias, relu)
+        return out if od is None else out.to(od)
 
     @staticmethod
     def corr(fmap1, fmap2, exact_f32=False):

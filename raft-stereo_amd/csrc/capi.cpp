@@ -740,6 +740,106 @@ extern "C" int rc_corr_lookup_conv_backward(const void *const *pyr, const int *w
                   "rc_corr_lookup_conv_backward: launch");
 }
 
+namespace {
+// Shared validation of rc_corr_lookup_chain_conv and its backward: the pair
+// layout in rows (2 levels, or 4 with level 2 given), rc_corr_lookup_chain's
+// checks.  Every refusal comes before the empty-problem return, so it does
+// not depend on B.  `io` is the tensor that must not be null (out / grad_out).
+int prep_chain_conv(const char *who, const void *const *pyr, const int *widths, const long *pyr_ld,
+                    int pyr_dtype, int levels, int radius, const float *coords_x, long coord_batch_stride,
+                    int B, int H, int W1, const void *io, bool allow_half, rc::LookupArgs &a, bool *empty) {
+    if (pyr_dtype & RC_OUT_CHANNELS_LAST)
+        return fail(RC_EUNSUPPORTED, "%s: RC_OUT_CHANNELS_LAST: the fused output is NCHW only", who);
+    if (pyr_dtype & (RC_LAYOUT_RECORDS | RC_LAYOUT_DISPARITY))
+        return fail(RC_EUNSUPPORTED, "%s: RC_LAYOUT_RECORDS / RC_LAYOUT_DISPARITY: the fused lookup reads "
+                    "the pair layout in rows only", who);
+    if (!allow_half && (pyr_dtype & RC_OUT_HALF))
+        return fail(RC_EUNSUPPORTED, "%s: RC_OUT_F16 / RC_OUT_BF16: grad_out and the gradients are fp32", who);
+    if ((pyr_dtype & RC_OUT_HALF) == RC_OUT_HALF)
+        return fail(RC_EINVAL, "%s: RC_OUT_F16 and RC_OUT_BF16 exclude each other", who);
+    const unsigned known = 0xFFu | RC_SHADOW | (unsigned)RC_OUT_HALF;
+    if ((unsigned)pyr_dtype & ~known)
+        return fail(RC_EINVAL, "%s: unknown pyr_dtype flag bits 0x%x", who, (unsigned)pyr_dtype & ~known);
+    int rc = prep_lookup(who, pyr, widths, pyr_ld, pyr_dtype, levels, radius, coords_x, coord_batch_stride,
+                         B, H, W1, io, a, empty, true);
+    if (rc) return rc;
+    if (levels == 3)
+        return fail(RC_EUNSUPPORTED, "%s: 3 levels are the level-1 chain; the fused pair kernels serve 2 "
+                    "levels, or 4 with level 2 given (rc_corr_lookup_conv reads a full pyramid)", who);
+    if (levels == 4 && !pyr[2])
+        return fail(RC_EUNSUPPORTED, "%s: 4 levels need level 2 (the pair layout); rc_corr_lookup_conv "
+                    "reads a full pyramid", who);
+    bool pair = false;
+    if ((rc = chain_kind(who, pyr, widths, levels, radius, &pair))) return rc;
+    if (!pair) return fail(RC_EUNSUPPORTED, "%s: the pair layout only (2 levels, or 4 with level 2 given)", who);
+    return RC_OK;
+}
+}  // namespace
+
+extern "C" int rc_corr_lookup_chain_conv(const void *const *pyr, const int *widths, const long *pyr_ld,
+                                         int pyr_dtype, int levels, int radius, const float *coords_x,
+                                         long coord_batch_stride, int B, int H, int W1,
+                                         const float *weight, const float *bias, int cout, int relu,
+                                         void *out, void *stream) {
+    g_err[0] = 0;
+    const char *who = "rc_corr_lookup_chain_conv";
+    rc::LookupArgs a;
+    bool empty;
+    int rc = prep_chain_conv(who, pyr, widths, pyr_ld, pyr_dtype, levels, radius, coords_x,
+                             coord_batch_stride, B, H, W1, out, true, a, &empty);
+    if (rc) return rc;
+    const bool bf16 = (pyr_dtype & 0xFF) == RC_BF16;
+    if (cout < 1) return fail(RC_EINVAL, "%s: cout=%d", who, cout);
+    if (empty) return RC_OK;
+    if (!weight) return fail(RC_EINVAL, "%s: null weight", who);
+    if ((rc = chain_strides(who, a, true, bf16))) return rc;
+    a.out = static_cast<float *>(out);
+    a.out_dt = out_dt_of(pyr_dtype);
+    return hip_rc(rc_launch_lookup_pair_conv(a, radius, bf16, weight, bias, cout, relu,
+                                             reinterpret_cast<hipStream_t>(stream)),
+                  "rc_corr_lookup_chain_conv: launch");
+}
+
+extern "C" int rc_corr_lookup_chain_conv_backward(const void *const *pyr, const int *widths,
+                                                  const long *pyr_ld, int pyr_dtype, int levels, int radius,
+                                                  const float *coords_x, long coord_batch_stride, int B,
+                                                  int H, int W1, const float *weight, const float *bias,
+                                                  int cout, int relu, const float *grad_out,
+                                                  float *grad_corr, float *grad_weight, float *grad_bias,
+                                                  float *workspace, void *stream) {
+    g_err[0] = 0;
+    const char *who = "rc_corr_lookup_chain_conv_backward";
+    rc::LookupArgs a;
+    bool empty;
+    int rc = prep_chain_conv(who, pyr, widths, pyr_ld, pyr_dtype, levels, radius, coords_x,
+                             coord_batch_stride, B, H, W1, grad_out, false, a, &empty);
+    if (rc) return rc;
+    const bool bf16 = (pyr_dtype & 0xFF) == RC_BF16;
+    if (cout < 1 || cout > (1 << 20)) return fail(RC_EINVAL, "%s: cout=%d", who, cout);
+    if (!grad_corr && !grad_weight && !grad_bias)
+        return fail(RC_EINVAL, "%s: none of grad_corr, grad_weight, grad_bias requested", who);
+    const bool sums = grad_weight || grad_bias;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (empty) {   // sums over no pixels
+        const size_t cin = (size_t)levels * (2 * radius + 1);
+        if (grad_weight)
+            if (hipError_t e = hipMemsetAsync(grad_weight, 0, (size_t)cout * cin * sizeof(float), s))
+                return hip_rc(e, "rc_corr_lookup_chain_conv_backward: memset");
+        if (grad_bias)
+            if (hipError_t e = hipMemsetAsync(grad_bias, 0, (size_t)cout * sizeof(float), s))
+                return hip_rc(e, "rc_corr_lookup_chain_conv_backward: memset");
+        return RC_OK;
+    }
+    if (!weight) return fail(RC_EINVAL, "%s: null weight", who);
+    if (sums && !workspace)
+        return fail(RC_EINVAL, "%s: grad_weight / grad_bias need a workspace of "
+                    "RC_LOOKUP_CONV_BWD_WS(P, cout, cin) floats", who);
+    if ((rc = chain_strides(who, a, true, bf16))) return rc;
+    return hip_rc(rc_launch_lookup_pair_conv_bwd(a, radius, bf16, weight, bias, cout, relu, grad_out,
+                                                 grad_corr, grad_weight, grad_bias, workspace, s),
+                  "rc_corr_lookup_chain_conv_backward: launch");
+}
+
 extern "C" int rc_convex_upsample(const float *flow, const float *mask, int N, int C, int H, int W,
                                   int factor, float *out, void *stream) {
     g_err[0] = 0;

@@ -254,6 +254,14 @@ hipError_t rc_launch_lookup_conv_bwd(const rc::LookupArgs &a, int radius, int py
                                      const float *b, int cout, int relu, const float *grad_out,
                                      float *grad_corr, float *grad_weight, float *grad_bias,
                                      float *workspace, hipStream_t s);
+// the fused lookup + convc1 on the pair layout (lookup_pair_conv.hip): a.out holds [B][cout][H][W1]
+// elements of a.out_dt; the backward takes rc_launch_lookup_conv_bwd's arguments
+hipError_t rc_launch_lookup_pair_conv(const rc::LookupArgs &a, int radius, int pyr_bf16, const float *w,
+                                      const float *b, int cout, int relu, hipStream_t s);
+hipError_t rc_launch_lookup_pair_conv_bwd(const rc::LookupArgs &a, int radius, int pyr_bf16, const float *w,
+                                          const float *b, int cout, int relu, const float *grad_out,
+                                          float *grad_corr, float *grad_weight, float *grad_bias,
+                                          float *workspace, hipStream_t s);
 hipError_t rc_launch_lookup_chain(const rc::LookupArgs &a, int radius, hipStream_t s);
 hipError_t rc_launch_lookup_pair(const rc::LookupArgs &a, int radius, int pyr_bf16, hipStream_t s);
 // the pair / records kernels with a.out_dt != 0 (called by rc_launch_lookup_pair; lookup_half.hip)

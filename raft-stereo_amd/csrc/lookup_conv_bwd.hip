@@ -26,14 +26,15 @@
 // LDS rows have a pitch of 68 floats: the 64 lanes of an operand read
 // (16 rows x 4 consecutive pixels) hit 64 distinct banks.  56.6 KB per
 // workgroup at CIN = 36: two workgroups per CU.
+// Everything after the recompute is conv_bwd_sums (lookup_conv_bwd.h), shared
+// with the pair-layout backward (lookup_pair_conv.hip), which also launches
+// the reduce kernel defined here (rc_launch_lookup_conv_bwd_reduce).
 // Built with -ffp-contract=off like lookup.hip (the lookup's op sequence).
 #include "common.h"
+#include "lookup_conv_bwd.h"   // conv_bwd_sums: everything after the corr recompute
 #include "lookup_level.h"
 
 namespace rc {
-
-constexpr int kCbwdPitch = 68;                 // LDS row pitch (floats)
-constexpr int kCbwdGTile = 16 * kCbwdPitch;    // one wave's g[16][64] tile
 
 template <int R, int NL, bool BF16>
 __global__ __launch_bounds__(256) void lookup_conv_bwd_kernel(LookupArgs a, const float *__restrict__ wgt,
@@ -42,13 +43,10 @@ __global__ __launch_bounds__(256) void lookup_conv_bwd_kernel(LookupArgs a, cons
                                                               float *__restrict__ gcorr,
                                                               float *__restrict__ ws) {
     constexpr int T = 2 * R + 1, CIN = NL * T;
-    constexpr int NT = (CIN + 1 + 15) / 16;          // column tiles: corr channels + the ones column
-    static_assert(NT * 4 * 64 <= kCbwdGTile, "fragment exchange reuses the g tile");
     __shared__ float s_corr[4 * CIN * kCbwdPitch];
     __shared__ float s_g[4 * kCbwdGTile];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const long long pblk = (long long)blockIdx.x * 256;
-    const long long p = pblk + tid;
+    const long long p = pblk + threadIdx.x;
     const bool active = p < a.P;
     const long long pp = active ? p : a.P - 1;
     const long long bimg = pp / a.HW, rem = pp - bimg * a.HW;
@@ -63,76 +61,7 @@ __global__ __launch_bounds__(256) void lookup_conv_bwd_kernel(LookupArgs a, cons
         for (int i = 0; i < NL; ++i)
             finish_level<R, BF16>(lw[i], a, i, pblk, lrow, [&](int t, float v) { corr[i * T + t] = v; });
     }
-    float *sc = s_corr + wave * CIN * kCbwdPitch, *sg = s_g + wave * kCbwdGTile;
-    if (ws) {
-        // lanes past the last pixel stand in for pixel P-1: zero, so that a
-        // non-finite corr there cannot reach the sums (their g is zero too)
-#pragma unroll
-        for (int k = 0; k < CIN; ++k) sc[k * kCbwdPitch + lane] = active ? corr[k] : 0.0f;
-    }
-    float gc[CIN];
-#pragma unroll
-    for (int k = 0; k < CIN; ++k) gc[k] = 0.0f;
-    const float *gop = gout + bimg * (long long)cout * a.HW + rem;
-    const int i16 = lane & 15, g4 = lane >> 4;
-    const long long wsn = (long long)cout * (CIN + 1);       // floats per workgroup slice
-    for (int c0 = 0; c0 < cout; c0 += 16) {
-#pragma unroll 1
-        for (int cc = 0; cc < 16; ++cc) {
-            const int c = c0 + cc;
-            float g = 0.0f;
-            if (c < cout) {                                   // block-uniform
-                const float *wr = wgt + c * CIN;
-                float acc = bias ? bias[c] : 0.0f;
-#pragma unroll
-                for (int k = 0; k < CIN; ++k) acc = fmaf(wr[k], corr[k], acc);
-                const float go = active ? gop[(long long)c * a.HW] : 0.0f;
-                g = (relu && !(acc > 0.0f)) ? 0.0f : go;
-                if (gcorr) {
-#pragma unroll
-                    for (int k = 0; k < CIN; ++k) gc[k] = fmaf(wr[k], g, gc[k]);
-                }
-            }
-            if (ws) sg[cc * kCbwdPitch + lane] = g;
-        }
-        if (!ws) continue;                                    // block-uniform
-        __syncthreads();
-        f32x4 acc[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[nt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const int px = 4 * s + g4;                        // lane (i16, g4) supplies k = g4 of step s
-            const float av = sg[i16 * kCbwdPitch + px];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const int j = 16 * nt + i16;
-                const float cv = sc[(j < CIN ? j : CIN - 1) * kCbwdPitch + px];
-                const float bv = j < CIN ? cv : (j == CIN ? 1.0f : 0.0f);
-                acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[nt], 0, 0, 0);
-            }
-        }
-        // the wave's fragments over its own (already read) g tile, then the
-        // four waves added in wave order: lane l, register r of tile nt is
-        // row 4 (l >> 4) + r, column 16 nt + (l & 15)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) sg[(nt * 4 + r) * 64 + lane] = acc[nt][r];
-        __syncthreads();
-        for (int e = tid; e < NT * 256; e += 256) {
-            const int q = e >> 6, l = e & 63;
-            const int c = c0 + 4 * (l >> 4) + (q & 3), j = 16 * (q >> 2) + (l & 15);
-            const float sum = ((s_g[e] + s_g[kCbwdGTile + e]) + s_g[2 * kCbwdGTile + e]) + s_g[3 * kCbwdGTile + e];
-            if (c < cout && j <= CIN) ws[(long long)blockIdx.x * wsn + (long long)c * (CIN + 1) + j] = sum;
-        }
-        __syncthreads();                                      // the tiles are rewritten next round
-    }
-    if (gcorr && active) {
-        float *gp = gcorr + bimg * (long long)CIN * a.HW + rem;
-#pragma unroll
-        for (int k = 0; k < CIN; ++k) gp[(long long)k * a.HW] = gc[k];
-    }
+    conv_bwd_sums<CIN>(corr, a, active, bimg, rem, s_corr, s_g, wgt, bias, cout, relu, gout, gcorr, ws);
 }
 
 // grad_weight[c][k] / grad_bias[c] = the sum over the nblk workgroup slices
@@ -205,9 +134,13 @@ hipError_t rc_launch_lookup_conv_bwd(const rc::LookupArgs &a, int radius, int py
         default: return hipErrorInvalidValue;
     }
     if (e != hipSuccess || !sums) return e;
-    const int cin = a.levels * (2 * radius + 1);
+    return rc_launch_lookup_conv_bwd_reduce(ws, (int)((a.P + 255) / 256), cout, a.levels * (2 * radius + 1),
+                                            grad_weight, grad_bias, s);
+}
+
+hipError_t rc_launch_lookup_conv_bwd_reduce(const float *ws, int nblk, int cout, int cin, float *grad_weight,
+                                            float *grad_bias, hipStream_t s) {
     const int n = cout * (cin + 1);
-    const int nblk = (int)((a.P + 255) / 256);
     hipLaunchKernelGGL(rc::lookup_conv_bwd_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, s, ws,
                        nblk, cout, cin, grad_weight, grad_bias);
     return hipGetLastError();

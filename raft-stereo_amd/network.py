@@ -236,7 +236,8 @@ class RAFTStereo(nn.Module):
     def __init__(self, args, corr_block=None, fuse_convc1=False, fuse_step=False, corr_out_dtype=None):
         super().__init__()
         self.args = args
-        # corr_out_dtype: the lookup output's dtype.  None:
+        # corr_out_dtype: the lookup output's dtype (with
+        # fuse_convc1: the fused lookup+convc1 output's, which convc2 reads).  None:
         # fp32, which convc1 casts under autocast.  "autocast": the autocast
         # dtype when args.mixed_precision runs on a GPU, so the lookup writes
         # what convc1 reads (same values, no cast kernel); fp32 otherwise.  A
@@ -302,8 +303,8 @@ class RAFTStereo(nn.Module):
         when grad is enabled."""
         a = self.args
         fmap1, fmap2, net_list, inp_list = self.features(image1, image2)
-        corr_fn = self.corr_block(fmap1, fmap2, radius=a.corr_radius, num_levels=a.corr_levels,
-                                  **self._corr_kwargs())
+        corr_kw = self._corr_kwargs()
+        corr_fn = self.corr_block(fmap1, fmap2, radius=a.corr_radius, num_levels=a.corr_levels, **corr_kw)
         coords0, coords1 = self.initialize_flow(net_list[0])
         if flow_init is not None:
             coords1 = coords1 + flow_init
@@ -323,9 +324,11 @@ class RAFTStereo(nn.Module):
                     predictions.append(flow)
             else:
                 if fused:                               # lookup + convc1 + ReLU, one launch
-                    # with grad enabled it carries rc_corr_lookup_conv_backward
+                    # with grad enabled it carries rc_corr_lookup_conv_backward;
+                    # corr_out_dtype: the fused kernel writes what convc2 reads
+                    # under autocast (the keyword only when the option is set)
                     corr = corr_fn.lookup_convc1(coords1, enc.convc1.weight, enc.convc1.bias,
-                                                 differentiable=torch.is_grad_enabled())
+                                                 differentiable=torch.is_grad_enabled(), **corr_kw)
                 else:
                     corr = corr_fn(coords1)             # the hot path, every iteration
                 flow = coords1 - coords0
