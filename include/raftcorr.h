@@ -51,18 +51,44 @@ extern "C" {
 /* Version 13 also covers rc_corr_lookup_chain_conv and
  * rc_corr_lookup_chain_conv_backward: they were added without changing any
  * existing entry point, flag or layout (purely additive), so the number did
- * not move.  A caller that needs them checks for the symbols. */
+ * not move.  A caller that needs them checks for the symbols.
+ * The element type RC_F16 was added the same way: a new value of an existing
+ * argument that a version-13 caller never passes (a library from before it
+ * answers RC_EINVAL "unknown dtype"), no entry point, flag or layout changed,
+ * so the number did not move for it either. */
 #define RC_ABI_VERSION 13
 
 /* element types */
 #define RC_F32  0
 #define RC_BF16 1
+/* IEEE fp16.  An fp16 pyramid is the bf16 pyramid's twin for an fp16-autocast
+ * network: the same bytes, 11 significant bits instead of 8, built on
+ * v_mfma_f32_16x16x32_f16 (the bf16 instruction's rate).  Level 0 is the fp32
+ * accumulator / sqrtf(D) rounded once to nearest even (fp16 subnormals kept,
+ * magnitudes above 65504 become +-inf: fp16 has 5 exponent bits where bf16 has
+ * 8); every higher level is fp16((x + y) * 0.5f) of the level below AS STORED
+ * (so +inf and -inf pool to NaN).  Accepted by
+ *   rc_corr_build         (fmap RC_F16, pyr RC_F16) and (fmap RC_F32, pyr
+ *                         RC_F16: fmaps rounded to fp16 on load), RC_SHADOW_LEVEL
+ *                         bits as for bf16;
+ *   rc_corr_pool;
+ *   rc_corr_lookup        (every level stored);
+ *   rc_corr_lookup_chain  on the pair layout only, as for bf16 (2 levels, or 4
+ *                         with levels 0 and 2 stored), with RC_SHADOW,
+ *                         RC_OUT_CHANNELS_LAST and RC_OUT_F16 / RC_OUT_BF16.
+ * RC_EUNSUPPORTED, before any launch, for: an fp32 pyramid from fp16 fmaps,
+ * any fp16 / bf16 mix, RC_LAYOUT_RECORDS, RC_LAYOUT_DISPARITY and
+ * RC_BUILD_EXACT_F32 in rc_corr_build; and as the pyramid type of every other
+ * entry point (rc_corr_lookup_step, rc_corr_lookup_conv,
+ * rc_corr_lookup_chain_conv and their backwards).  rc_corr_build_backward is
+ * unchanged: it takes fp32 fmaps (widen fp16 ones). */
+#define RC_F16  2
 
 /* Flags OR-ed into a pyr_dtype argument (ABI v5): RC_SHADOW_LEVEL(l) says
  * stored pyramid level l has a line-phase SHADOW copy (RC_SHADOW: every
  * stored level) -- the same rows, at byte offset
  * RC_SHADOW_OFFSET(rows, ld, esize) from the level's base (rows = B*H*W1,
- * ld = its row stride in elements, esize = 4 for RC_F32, 2 for RC_BF16), so
+ * ld = its row stride in elements, esize = 4 for RC_F32, 2 for RC_BF16 / RC_F16), so
  * the allocation holds rows*ld*esize bytes, a gap, then the copy, shifted by
  * half a 128-byte line against the primary when the base is 128-B aligned.
  * rc_corr_build writes both copies; the pair kernel of rc_corr_lookup_chain /
@@ -171,7 +197,8 @@ const char *rc_last_error(void);
 
 /* Volume + pyramid (model.py:284-295, :318-326).
  *   fmap1: [B][D][H][W1], fmap2: [B][D][H][W2], contiguous, element type
- *          fmap_dtype (RC_F32, or RC_BF16 for the bf16 MFMA path).
+ *          fmap_dtype (RC_F32, or RC_BF16 for the bf16 MFMA path, or RC_F16
+ *          with an RC_F16 pyramid for the fp16 one).
  *   pyr[l], l < nbuf: device buffers of B*H*W1 rows of W2 >> l elements of
  *          pyr_dtype, row stride pyr_ld[l] elements (>= W2 >> l; NULL pyr_ld =
  *          dense rows).  Level 0 is the volume divided by sqrtf(D), level l+1
@@ -187,7 +214,9 @@ const char *rc_last_error(void);
  *   kernel v_mfma_f32_16x16x4_f32 instead).  Any bf16 operand (bf16 fmaps, or a
  *   bf16 pyramid requested for fp32 fmaps, which are rounded to bf16 on
  *   load) runs the bf16 MFMA kernel (v_mfma_f32_16x16x32_bf16, fp32
- *   accumulation); pooling is done on the fp32 accumulators either way. */
+ *   accumulation); pooling is done on the fp32 accumulators either way.
+ *   An RC_F16 pyramid (see RC_F16) runs the same kernels on
+ *   v_mfma_f32_16x16x32_f16. */
 int rc_corr_build(const void *fmap1, const void *fmap2, int fmap_dtype,
                   int B, int D, int H, int W1, int W2,
                   void *const *pyr, const long *pyr_ld, int nbuf, int pyr_dtype,
@@ -195,7 +224,7 @@ int rc_corr_build(const void *fmap1, const void *fmap2, int fmap_dtype,
 
 /* One pooling step (model.py:294): out[p][j] = (in[p][2j] + in[p][2j+1]) / 2,
  * j < W_in/2, for p < rows; row strides ld_in / ld_out elements.  dtype
- * RC_F32 or RC_BF16 (bf16 rounds once). */
+ * RC_F32, RC_BF16 or RC_F16 (the 16-bit types round once). */
 int rc_corr_pool(const void *in, long ld_in, void *out, long ld_out, long rows,
                  int W_in, int dtype, void *stream);
 

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "_build", "libraftcorr.so")
 DEV_LIB_PATH = os.path.join(_HERE, "_build", "libraftcorr_dev.so")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "raftcorr.h")
 
-RC_F32, RC_BF16 = 0, 1
+RC_F32, RC_BF16, RC_F16 = 0, 1, 2
 RC_OK, RC_EINVAL, RC_EUNSUPPORTED, RC_EHIP = 0, 1, 2, 3
 RC_MAX_LEVELS = 8
 ABI_VERSION = 13

@@ -40,6 +40,9 @@ bf16/fp16 fmaps are accepted (the reference crashes on them, SURVEY.md
 Appendix A D9; their gradients are computed in fp32): they, or
 an explicit ``pyramid_dtype=torch.bfloat16``, select the bf16 MFMA kernel and
 a bf16 pyramid (bf16-level tolerance).
+``pyramid_dtype=torch.float16`` (opt-in) selects the fp16
+MFMA kernel and an fp16 pyramid instead: fp16 fmaps go to the kernel as they
+are, fp32 ones are rounded on load, values above 65504 store +-inf.
 """
 import warnings
 
@@ -71,7 +74,9 @@ def _dtype_code(dt):
         return _lib.RC_F32
     if dt == torch.bfloat16:
         return _lib.RC_BF16
-    raise TypeError(f"raft_stereo_amd: unsupported dtype {dt} (float32 or bfloat16)")
+    if dt == torch.float16:
+        return _lib.RC_F16
+    raise TypeError(f"raft_stereo_amd: unsupported dtype {dt} (float32, bfloat16 or float16)")
 
 
 def _check_out_dtype(out_dtype):
@@ -106,11 +111,23 @@ def _check_fmaps(fmap1, fmap2):
     return B, D, H, W1, W2
 
 
-def _prep_fmap(f):
+def _check_f16_pyramid_fmaps(fmap1, fmap2):
+    """An fp16 pyramid is built from fp16 or fp32 fmaps: the fp16 MFMA takes
+    one operand type, and bf16 values need not fit fp16's range."""
+    for name, f in (("fmap1", fmap1), ("fmap2", fmap2)):
+        if getattr(f, "dtype", None) == torch.bfloat16:
+            raise ValueError(f"CorrBlock1D: pyramid_dtype=torch.float16 with bfloat16 {name}: fp16 and bf16 "
+                             "do not mix; pass fp16 or fp32 fmaps, or pyramid_dtype=torch.bfloat16")
+
+
+def _prep_fmap(f, pyramid_dtype=None):
     # fp32 and bf16 go to the kernels as they are; fp16 (default autocast)
-    # is widened to fp32 and then rounded to bf16 on load by the bf16 kernel.
+    # is widened to fp32 and then rounded to bf16 on load by the bf16 kernel
+    # -- unless the pyramid is fp16 too: then the fp16 MFMA kernel reads it
+    # as it is (no cast kernels, 2-byte fmap reads).
     if f.dtype == torch.float16:
-        f = f.float()
+        if pyramid_dtype != torch.float16:
+            f = f.float()
     elif f.dtype not in (torch.float32, torch.bfloat16):
         raise TypeError(f"raft_stereo_amd: unsupported fmap dtype {f.dtype}")
     return f.contiguous()
@@ -186,7 +203,9 @@ def build_pyramid(fmap1, fmap2, nbuf, pyramid_dtype=torch.float32, pad=True, ski
             "avg_pool2d output size is too small (model.py:294)")
     if nbuf > _lib.RC_MAX_LEVELS:
         raise RuntimeError(f"CorrBlock1D: at most {_lib.RC_MAX_LEVELS - 1} levels supported")
-    f1, f2 = _prep_fmap(fmap1), _prep_fmap(fmap2)
+    if pyramid_dtype == torch.float16:
+        _check_f16_pyramid_fmaps(fmap1, fmap2)
+    f1, f2 = _prep_fmap(fmap1, pyramid_dtype), _prep_fmap(fmap2, pyramid_dtype)
     if f1.dtype != f2.dtype:
         f1, f2 = f1.float(), f2.float()
     P = B * H * W1
@@ -208,7 +227,7 @@ def build_pyramid(fmap1, fmap2, nbuf, pyramid_dtype=torch.float32, pad=True, ski
 
 def pool_level(src):
     """One pyramid step (model.py:294) with rc_corr_pool: (P,1,1,W) -> (P,1,1,W//2)
-    in a row-padded buffer, the same fp32 (or bf16) ops as the build epilogue."""
+    in a row-padded buffer, the same fp32 (or bf16 / fp16) ops as the build epilogue."""
     P, W = src.shape[0], src.shape[-1]
     out = _level_buffer(P, W // 2, src.dtype, src.device, True)
     if P == 0:
@@ -858,7 +877,8 @@ def default_shadow_levels(P, W2, num_levels, pyramid_dtype):
     """Stored levels that get an RC_SHADOW copy by default (measured per
     config with the corr step = build + 32 lookups, tools/shadow_probe.py,
     profiles/r03/shadow_*.log): level 2 of a 4-level pair
-    layout always; level 0 only for a bf16 pyramid larger than the 256 MiB
+    layout always; level 0 only for a bf16 (or fp16: the same bytes) pyramid
+    larger than the 256 MiB
     Infinity Cache.  A bf16 span (40 B) then always fits one 128-B line, which
     pays for the copy's writes (config 3, B=64: 6227 us per step with levels
     0 + 2, 6288 with level 2 only); an fp32 level 0 saves too little per
@@ -867,7 +887,7 @@ def default_shadow_levels(P, W2, num_levels, pyramid_dtype):
     kernel's 4 GiB window."""
     es = torch.tensor([], dtype=pyramid_dtype).element_size()
     lv = [2] if num_levels == 4 else []
-    if pyramid_dtype == torch.bfloat16 and P * W2 * es > (256 << 20):
+    if es == 2 and P * W2 * es > (256 << 20):
         lv.insert(0, 0)
     return tuple(l for l in lv if shadow_fits(P, W2 >> l, pyramid_dtype))
 
@@ -1076,6 +1096,24 @@ class CorrBlock1D:
         self.out_dtype = out_dtype
         self.num_levels = num_levels
         self.radius = radius
+        # pyramid_dtype=torch.float16 (opt-in): the fp16 MFMA
+        # build and an fp16 pyramid, for the fp16 fmaps of an fp16-autocast
+        # network (fp32 fmaps are rounded on load).  The bf16 pyramid's bytes,
+        # 11 significant bits instead of 8; values above 65504 store +-inf.
+        # Served in rows by the pair lookup (2 / 4 levels) and the per-level
+        # lookup; what has no fp16 kernel is refused here or at the call,
+        # never answered from a bf16 pyramid.
+        if pyramid_dtype == torch.float16:
+            _check_f16_pyramid_fmaps(fmap1, fmap2)
+            if layout in ("records", "disparity"):
+                raise ValueError(f"CorrBlock1D: layout={layout!r} with pyramid_dtype=torch.float16: the "
+                                 "records hold bf16 and the disparity-major levels fp32; an fp16 pyramid "
+                                 "is stored in rows")
+            if exact_f32:
+                raise ValueError("CorrBlock1D: exact_f32=True with pyramid_dtype=torch.float16: the fp16 "
+                                 "pyramid is built on the fp16 MFMA")
+            if layout == "auto":
+                layout = "rows"
         # check_finite (opt-in): the split-bf16 default gives NaN
         # where the reference's fp32 einsum gives +-inf for inf fmap entries
         # (pinned by tests/test_split_gpu.py); with
@@ -1144,10 +1182,10 @@ class CorrBlock1D:
         # levels are built only when ``corr_pyramid`` is read (``lazy_levels``,
         # default on in that case): same values, same shapes, pooled by the
         # same fp32 ops.
-        # (bf16 pyramids: the pair layout only -- 2 or 4 levels)
+        # (bf16 and fp16 pyramids: the pair layout only -- 2 or 4 levels)
         self._chain = (1 <= radius <= 4 and fmap2.shape[-1] <= 65536 and
                        (num_levels in (2, 3, 4) if pyramid_dtype == torch.float32 else
-                        num_levels in (2, 4) if pyramid_dtype == torch.bfloat16 else False))
+                        num_levels in (2, 4) if pyramid_dtype in (torch.bfloat16, torch.float16) else False))
         # low_latency (small inputs, e.g. the realtime config): store the
         # levels a lookup reads and use the per-level lookup, whose launcher gives each level
         # its own wave below 64K pixels (lookup_levelpar_kernel, DESIGN.md
@@ -1330,6 +1368,9 @@ class CorrBlock1D:
         ``(corr, coords1_new, flow)``, each bit-identical to the unfused ops.
         ``delta=None`` skips the update (first iteration); ``out=coords1``
         updates in place.  Inference only."""
+        if self.pyramid_dtype == torch.float16:
+            raise RuntimeError("CorrBlock1D.lookup_step: not available with pyramid_dtype=torch.float16 "
+                               "(no fp16-pyramid step kernel); call the block")
         if self._token is not None and torch.is_grad_enabled():
             raise RuntimeError("CorrBlock1D.lookup_step is inference-only")
         if self._sheared is not None:
@@ -1421,6 +1462,9 @@ class CorrBlock1D:
         the fp32 fused result followed by the cast: the incoming gradient is
         widened to fp32."""
         od = _check_out_dtype(out_dtype)
+        if self.pyramid_dtype == torch.float16:
+            raise RuntimeError("CorrBlock1D.lookup_convc1: not available with pyramid_dtype=torch.float16 "
+                               "(no fp16-pyramid fused kernel); use convc1(block(coords))")
         grad = torch.is_grad_enabled()
         if not differentiable and grad and (self._token is not None or weight.requires_grad):
             raise RuntimeError("CorrBlock1D.lookup_convc1 is inference-only; use "

@@ -69,6 +69,9 @@ int check_flags(const char *who, int pyr_dtype, bool allow_cl, bool build = fals
     return RC_OK;
 }
 
+// the element types are the kernels' element kinds (common.h)
+static_assert(RC_F32 == rc::kF32 && RC_BF16 == rc::kBF16 && RC_F16 == rc::kF16, "element kinds");
+
 bool is_pow2_float(float v) {
     int e;
     return std::frexp(v, &e) == 0.5f;
@@ -100,10 +103,28 @@ extern "C" int rc_corr_build(const void *fmap1, const void *fmap2, int fmap_dtyp
                     "rc_corr_build: pyramid level %d of width %d would be empty "
                     "(avg_pool2d output size too small, model.py:294)",
                     nbuf - 1, W2);
-    if (fmap_dtype != RC_F32 && fmap_dtype != RC_BF16)
+    if (fmap_dtype != RC_F32 && fmap_dtype != RC_BF16 && fmap_dtype != RC_F16)
         return fail(RC_EINVAL, "rc_corr_build: unknown fmap dtype %d", fmap_dtype);
-    if (pyr_dtype != RC_F32 && pyr_dtype != RC_BF16)
+    if (pyr_dtype != RC_F32 && pyr_dtype != RC_BF16 && pyr_dtype != RC_F16)
         return fail(RC_EINVAL, "rc_corr_build: unknown pyramid dtype %d", pyr_dtype);
+    if (fmap_dtype == RC_F16 || pyr_dtype == RC_F16) {
+        // RC_F16: an fp16 pyramid from fp16 fmaps, or from fp32 fmaps rounded on load
+        if (pyr_dtype == RC_F32)
+            return fail(RC_EUNSUPPORTED, "rc_corr_build: fp16 fmaps with an fp32 pyramid: widen the fmaps, or "
+                        "ask for an RC_F16 pyramid");
+        if (fmap_dtype == RC_BF16 || pyr_dtype == RC_BF16)
+            return fail(RC_EUNSUPPORTED, "rc_corr_build: fp16 and bf16 do not mix (fmap dtype %d, pyramid "
+                        "dtype %d): one MFMA operand type per build", fmap_dtype, pyr_dtype);
+        if (rec)
+            return fail(RC_EUNSUPPORTED, "rc_corr_build: RC_LAYOUT_RECORDS holds bf16 elements; an RC_F16 "
+                        "pyramid is stored in rows");
+        if (disp)
+            return fail(RC_EUNSUPPORTED, "rc_corr_build: RC_LAYOUT_DISPARITY holds fp32 elements; an RC_F16 "
+                        "pyramid is stored in rows");
+        if (exact_f32)
+            return fail(RC_EUNSUPPORTED, "rc_corr_build: RC_BUILD_EXACT_F32 selects the fp32 MFMA kernel; an "
+                        "RC_F16 pyramid is built on the fp16 MFMA");
+    }
     if (!pyr) return fail(RC_EINVAL, "rc_corr_build: null pyramid array");
     if (disp) {   // RC_LAYOUT_DISPARITY: the split build's pair layout only
         if (fmap_dtype != RC_F32 || pyr_dtype != RC_F32 || exact_f32 || shmask)
@@ -165,7 +186,7 @@ extern "C" int rc_corr_build(const void *fmap1, const void *fmap2, int fmap_dtyp
         a.lvl[l] = pyr[l];
         a.ld[l] = pyr_ld ? pyr_ld[l] : (W2 >> l);
         if ((shmask >> l & 1u) && pyr[l])
-            a.shadow[l] = shadow_offset((long long)B * H * W1, a.ld[l], pyr_dtype == RC_BF16 ? 2 : 4);
+            a.shadow[l] = shadow_offset((long long)B * H * W1, a.ld[l], pyr_dtype != RC_F32 ? 2 : 4);
         if (disp && pyr[l]) a.shk[l] = RC_SHEAR_ROWS(W2, W1, l);
     }
     a.tiles_m = (W1 + 127) / 128;
@@ -173,16 +194,17 @@ extern "C" int rc_corr_build(const void *fmap1, const void *fmap2, int fmap_dtyp
     a.sq = std::sqrt((float)D);                 // torch.sqrt(torch.tensor(D).float()), :326
     a.pow2 = is_pow2_float(a.sq) ? 1 : 0;
     a.scale = 1.0f / a.sq;                      // exact when pow2
-    a.pyr_bf16 = pyr_dtype == RC_BF16;
+    a.pyr_bf16 = pyr_dtype;                     // the element kind
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // fp32 fmaps + fp32 pyramid: exact fp32 MFMA.  bf16 fmaps, or a bf16
-    // pyramid (bf16-level tolerance requested), take the bf16 MFMA kernel.
-    const bool bf16_mma = fmap_dtype == RC_BF16 || pyr_dtype == RC_BF16;
+    // pyramid (bf16-level tolerance requested), take the bf16 MFMA kernel;
+    // an fp16 pyramid (from fp16 or fp32 fmaps) its fp16 twin.
+    const bool bf16_mma = fmap_dtype != RC_F32 || pyr_dtype != RC_F32;
     // fp32: the split-bf16 kernel (fp32 accuracy, volume_split.hip) unless the
     // exact fp32 MFMA kernel is asked for or the shape is outside the split
     // kernel's addressing (hipErrorNotSupported: nothing was launched)
     hipError_t e = hipErrorNotSupported;
-    if (bf16_mma) e = rc_launch_build_bf16mma(a, fmap_dtype == RC_BF16, s);
+    if (bf16_mma) e = rc_launch_build_bf16mma(a, fmap_dtype != RC_F32, s);
     else if (!exact_f32) e = rc_launch_build_split(a, s);
     if (e == hipErrorNotSupported && disp)
         return fail(RC_EUNSUPPORTED, "rc_corr_build: RC_LAYOUT_DISPARITY: shape outside the split build");
@@ -216,11 +238,11 @@ extern "C" int rc_corr_pool(const void *in, long ld_in, void *out, long ld_out, 
     if (rows < 0 || W_in < 2 || ld_in < W_in || ld_out < W_in / 2)
         return fail(RC_EINVAL, "rc_corr_pool: bad shape rows=%ld W_in=%d ld_in=%ld ld_out=%ld", rows,
                     W_in, ld_in, ld_out);
-    if (dtype != RC_F32 && dtype != RC_BF16)
+    if (dtype != RC_F32 && dtype != RC_BF16 && dtype != RC_F16)
         return fail(RC_EINVAL, "rc_corr_pool: unknown dtype %d", dtype);
     if (rows == 0) return RC_OK;
     if (!in || !out) return fail(RC_EINVAL, "rc_corr_pool: null pointer");
-    return hip_rc(rc_launch_pool(in, ld_in, out, ld_out, rows, W_in, dtype == RC_BF16,
+    return hip_rc(rc_launch_pool(in, ld_in, out, ld_out, rows, W_in, dtype,
                                  reinterpret_cast<hipStream_t>(stream)),
                   "rc_corr_pool: launch");
 }
@@ -230,7 +252,7 @@ namespace {
 int prep_lookup(const char *who, const void *const *pyr, const int *widths, const long *pyr_ld,
                 int pyr_dtype, int levels, int radius, const float *coords_x,
                 long coord_batch_stride, int B, int H, int W1, const void *out, rc::LookupArgs &a,
-                bool *empty, bool allow_null = false) {
+                bool *empty, bool allow_null = false, bool allow_f16 = false) {
     *empty = false;
     const bool disp = (pyr_dtype & RC_LAYOUT_DISPARITY) != 0;     // rows of W1 (or more) per diagonal
     const bool rec = (pyr_dtype & RC_LAYOUT_RECORDS) != 0;        // pyr[0] = the records
@@ -240,8 +262,11 @@ int prep_lookup(const char *who, const void *const *pyr, const int *widths, cons
         return fail(RC_EINVAL, "%s: levels=%d outside 1..%d", who, levels, RC_MAX_LEVELS);
     if (radius < 1 || radius > 8)
         return fail(RC_EUNSUPPORTED, "%s: radius=%d outside 1..8", who, radius);
-    if (pyr_dtype != RC_F32 && pyr_dtype != RC_BF16)
+    if (pyr_dtype != RC_F32 && pyr_dtype != RC_BF16 && pyr_dtype != RC_F16)
         return fail(RC_EINVAL, "%s: unknown pyramid dtype %d", who, pyr_dtype);
+    if (pyr_dtype == RC_F16 && !allow_f16)   // refused whatever the size, before any launch
+        return fail(RC_EUNSUPPORTED, "%s: an RC_F16 pyramid is read by rc_corr_lookup and "
+                    "rc_corr_lookup_chain only", who);
     if (B < 0 || H < 0 || W1 < 0)
         return fail(RC_EINVAL, "%s: bad shape B=%d H=%d W1=%d", who, B, H, W1);
     if (!pyr || !widths) return fail(RC_EINVAL, "%s: null pyramid/width array", who);
@@ -285,7 +310,7 @@ int prep_lookup(const char *who, const void *const *pyr, const int *widths, cons
             return fail(RC_EINVAL, "%s: level %d row stride %lld < width %d", who, i, a.ld[i],
                         widths[i]);
         if (shmask >> i & 1u) {
-            const int es = pyr_dtype == RC_BF16 ? 2 : 4;
+            const int es = pyr_dtype != RC_F32 ? 2 : 4;
             a.shadow[i] = shadow_offset(P, a.ld[i], es);
             // the pair kernel addresses both copies with 32-bit buffer offsets
             if (a.shadow[i] + P * a.ld[i] * es > 0xFFFFFF00LL)
@@ -328,7 +353,7 @@ int chain_kind(const char *who, const void *const *pyr, const int *widths, int l
 }
 
 // Row strides the chain kernels read with 16-B chunks must be whole chunks
-// (multiples of 4 fp32 / 8 bf16 elements).
+// (multiples of 4 fp32 / 8 bf16 or fp16 elements).
 int chain_strides(const char *who, const rc::LookupArgs &a, bool pair, bool bf16 = false) {
     const int need[2] = {0, pair ? 2 : 1};
     const int epc = bf16 ? 8 : 4;
@@ -351,12 +376,13 @@ extern "C" int rc_corr_lookup(const void *const *pyr, const int *widths, const l
     bool empty;
     if (int e = check_flags("rc_corr_lookup", pyr_dtype, false)) return e;
     int rc = prep_lookup("rc_corr_lookup", pyr, widths, pyr_ld, pyr_dtype, levels, radius, coords_x,
-                         coord_batch_stride, B, H, W1, out, a, &empty);
+                         coord_batch_stride, B, H, W1, out, a, &empty, false, true);
     if (rc || empty) return rc;
     pyr_dtype &= 0xFF;
     a.out = out;
-    return hip_rc(rc_launch_lookup(a, radius, pyr_dtype == RC_BF16,
-                                   reinterpret_cast<hipStream_t>(stream)),
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    return hip_rc(pyr_dtype == RC_F16 ? rc_launch_lookup_f16pyr(a, radius, s)
+                                      : rc_launch_lookup(a, radius, pyr_dtype == RC_BF16, s),
                   "rc_corr_lookup: launch");
 }
 
@@ -369,7 +395,7 @@ extern "C" int rc_corr_lookup_chain(const void *const *pyr, const int *widths, c
     bool empty;
     if (int e = check_flags("rc_corr_lookup_chain", pyr_dtype, true, false, true, true)) return e;
     int rc = prep_lookup("rc_corr_lookup_chain", pyr, widths, pyr_ld, pyr_dtype, levels, radius,
-                         coords_x, coord_batch_stride, B, H, W1, out, a, &empty, true);
+                         coords_x, coord_batch_stride, B, H, W1, out, a, &empty, true, true);
     if (rc) return rc;
     const bool cl = (pyr_dtype & RC_OUT_CHANNELS_LAST) != 0;
     const int out_dt = out_dt_of(pyr_dtype);
@@ -385,8 +411,8 @@ extern "C" int rc_corr_lookup_chain(const void *const *pyr, const int *widths, c
     if (disp && (!pair || pyr_dtype != RC_F32 || cl || shadowed))
         return fail(RC_EUNSUPPORTED, "rc_corr_lookup_chain: RC_LAYOUT_DISPARITY needs the fp32 pair layout "
                     "(2 levels, or 4 with level 2 given), NCHW output and no shadow copies");
-    if (pyr_dtype == RC_BF16 && !pair)
-        return fail(RC_EUNSUPPORTED, "rc_corr_lookup_chain: a bf16 pyramid needs the pair layout "
+    if (pyr_dtype != RC_F32 && !pair)
+        return fail(RC_EUNSUPPORTED, "rc_corr_lookup_chain: a bf16 / fp16 pyramid needs the pair layout "
                     "(2 levels, or 4 with level 2 given)");
     if (cl && !pair)
         return fail(RC_EUNSUPPORTED, "rc_corr_lookup_chain: RC_OUT_CHANNELS_LAST needs the pair layout");
@@ -397,9 +423,10 @@ extern "C" int rc_corr_lookup_chain(const void *const *pyr, const int *widths, c
     a.out = static_cast<float *>(out);
     a.out_cl = cl;
     a.out_dt = out_dt;
-    if (!rec && (rc = chain_strides("rc_corr_lookup_chain", a, pair, pyr_dtype == RC_BF16))) return rc;
+    if (!rec && (rc = chain_strides("rc_corr_lookup_chain", a, pair, pyr_dtype != RC_F32))) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    return hip_rc(pair ? rc_launch_lookup_pair(a, radius, pyr_dtype == RC_BF16, s)
+    return hip_rc(pair ? (pyr_dtype == RC_F16 ? rc_launch_lookup_pair_f16pyr(a, radius, s)
+                                              : rc_launch_lookup_pair(a, radius, pyr_dtype == RC_BF16, s))
                        : rc_launch_lookup_chain(a, radius, s),
                   "rc_corr_lookup_chain: launch");
 }

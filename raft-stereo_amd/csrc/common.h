@@ -87,6 +87,35 @@ __device__ __forceinline__ uint16_t f32_to_bf16(float f) {
 // fp32 value rounded to bf16 precision (RNE), kept in fp32.
 __device__ __forceinline__ float round_bf16(float f) { return bf16_to_f32(f32_to_bf16(f)); }
 
+// Element kind of a pyramid (or of 16-bit feature maps): the C-ABI's RC_F32 /
+// RC_BF16 / RC_F16 codes.  A `bool bf16` of older code converts to kF32 / kBF16.
+enum : int { kF32 = 0, kBF16 = 1, kF16 = 2 };
+
+// fp16 helpers: the hardware convert (v_cvt_f16_f32) rounds to nearest even,
+// keeps +-inf, overflows to +-inf above 65504 and keeps subnormals (the
+// kernels' fp16 denormal mode is IEEE) -- what Tensor.half() does.  The
+// opaque copy keeps the fp32 value a value of its own: the compiler may not
+// fold the multiply that made it and this convert into one v_fma_mixlo_f16
+// (one rounding instead of two; see out_cvt in lookup_pair.h).
+__device__ __forceinline__ float f16_to_f32(uint16_t v) { return (float)__builtin_bit_cast(_Float16, v); }
+__device__ __forceinline__ uint16_t f32_to_f16(float f) {
+    asm("" : "+v"(f));
+    return __builtin_bit_cast(uint16_t, (_Float16)f);
+}
+__device__ __forceinline__ float round_f16(float f) { return f16_to_f32(f32_to_f16(f)); }
+
+// The same three for an element kind EK (kBF16 or kF16), compile-time or not.
+__device__ __forceinline__ float h16_to_f32(uint16_t v, int ek) { return ek == kF16 ? f16_to_f32(v) : bf16_to_f32(v); }
+__device__ __forceinline__ uint16_t f32_to_h16(float f, int ek) { return ek == kF16 ? f32_to_f16(f) : f32_to_bf16(f); }
+__device__ __forceinline__ float round_h16(float f, int ek) { return ek == kF16 ? round_f16(f) : round_bf16(f); }
+// the two halves of a packed pair, widened
+__device__ __forceinline__ float h16_lo(uint32_t u, int ek) {
+    return ek == kF16 ? f16_to_f32((uint16_t)u) : __builtin_bit_cast(float, u << 16);
+}
+__device__ __forceinline__ float h16_hi(uint32_t u, int ek) {
+    return ek == kF16 ? f16_to_f32((uint16_t)(u >> 16)) : __builtin_bit_cast(float, u & 0xFFFF0000u);
+}
+
 // v / sqrt(D) as the reference's division (model.py:326): a multiply by the
 // exact 1/sqrt(D) when D is a power of four (a.pow2), the correctly rounded
 // division otherwise.  One wave-uniform branch around the whole group: the
@@ -115,7 +144,7 @@ struct BuildArgs {
     float scale;              // exact reciprocal of sqrt(D) when pow2 != 0
     float sq;                 // sqrtf(D)
     int pow2;                 // sqrt(D) is a power of two -> multiply is exact
-    int pyr_bf16;             // store pyramid as bf16
+    int pyr_bf16;             // pyramid element kind: kF32, kBF16 or kF16 (non-zero: a 16-bit pyramid)
     int stagger;              // reserved (no reader): keeps the kernarg offsets of the fields below
     // line-phase shadow copies (ABI v5, RC_SHADOW): a stored level l is also
     // written at (char*)lvl[l] + shadow[l] bytes (0 = no copy)
@@ -242,9 +271,13 @@ inline int device_cus() {
 // Host-side launchers (defined in the .hip files, called by capi.cpp).
 hipError_t rc_launch_build_f32(const rc::BuildArgs &a, hipStream_t s);
 hipError_t rc_launch_build_split(rc::BuildArgs &a, hipStream_t s);     // may lower a.nfused
-hipError_t rc_launch_build_bf16mma(rc::BuildArgs &a, int in_bf16, hipStream_t s);   // may lower a.nfused
+// in_16: the fmaps hold 16-bit elements of the pyramid's kind (a.pyr_bf16), else fp32
+hipError_t rc_launch_build_bf16mma(rc::BuildArgs &a, int in_16, hipStream_t s);   // may lower a.nfused
+// the same for an fp16 pyramid (a.pyr_bf16 == kF16; volume_half.hip)
+hipError_t rc_launch_build_f16mma(rc::BuildArgs &a, int in_16, hipStream_t s);
+// ek: element kind (kF32 / kBF16 / kF16)
 hipError_t rc_launch_pool(const void *in, long long ld_in, void *out, long long ld_out, long rows,
-                          int W_in, int bf16, hipStream_t s);
+                          int W_in, int ek, hipStream_t s);
 hipError_t rc_launch_lookup(const rc::LookupArgs &a, int radius, int pyr_bf16, hipStream_t s);
 hipError_t rc_launch_lookup_conv(const rc::LookupArgs &a, int radius, int pyr_bf16, const float *w,
                                  const float *b, int cout, int relu, float *out, hipStream_t s);
@@ -266,6 +299,9 @@ hipError_t rc_launch_lookup_chain(const rc::LookupArgs &a, int radius, hipStream
 hipError_t rc_launch_lookup_pair(const rc::LookupArgs &a, int radius, int pyr_bf16, hipStream_t s);
 // the pair / records kernels with a.out_dt != 0 (called by rc_launch_lookup_pair; lookup_half.hip)
 hipError_t rc_launch_lookup_pair_half(const rc::LookupArgs &a, int radius, int pyr_bf16, hipStream_t s);
+// an fp16 pyramid (RC_F16; lookup_f16pyr.hip): the per-level lookup and the pair lookup, every a.out_dt
+hipError_t rc_launch_lookup_f16pyr(const rc::LookupArgs &a, int radius, hipStream_t s);
+hipError_t rc_launch_lookup_pair_f16pyr(const rc::LookupArgs &a, int radius, hipStream_t s);
 hipError_t rc_launch_lookup_bwd(const rc::LookupBwdArgs &a, int radius, hipStream_t s);
 // fills a.pix / rowbase / S / lds_floats from W, radius, levels
 hipError_t rc_launch_lookup_bwd_calls(rc::LookupBwdCallsArgs &a, int radius, int levels, hipStream_t s);

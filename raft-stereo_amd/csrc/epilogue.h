@@ -16,18 +16,19 @@ enum { kModeNoLoads = 1, kModeNoStores = 2, kModeNoMath = 4, kModeAlignedSrc = 8
        kModeL2Stores = 65536, kModeFastEpi = 262144,
        kModeRecords = 1 << 23, kModeRecNoStore = 1 << 24, kModeRecNoEmit = 1 << 25 };
 
-// VW consecutive level values -> memory (fp32, or bf16 rounded to nearest even).
+// VW consecutive level values -> memory: fp32 (ek = kF32), or bf16 / fp16
+// rounded to nearest even (ek = kBF16 / kF16, the pyramid's element kind).
 template <int VW>
-__device__ __forceinline__ void store_vec1(void *lvl, bool bf16, long long g, const float *v) {
-    if (bf16) {
+__device__ __forceinline__ void store_vec1(void *lvl, int ek, long long g, const float *v) {
+    if (ek) {
         uint16_t *d = reinterpret_cast<uint16_t *>(lvl) + g;
         if constexpr (VW == 1) {
-            d[0] = f32_to_bf16(v[0]);
+            d[0] = f32_to_h16(v[0], ek);
         } else {
             unsigned w[VW / 2];
 #pragma unroll
             for (int k = 0; k < VW / 2; ++k)
-                w[k] = (unsigned)f32_to_bf16(v[2 * k]) | ((unsigned)f32_to_bf16(v[2 * k + 1]) << 16);
+                w[k] = (unsigned)f32_to_h16(v[2 * k], ek) | ((unsigned)f32_to_h16(v[2 * k + 1], ek) << 16);
             if constexpr (VW == 8) *reinterpret_cast<uint4 *>(d) = uint4{w[0], w[1], w[2], w[3]};
             else if constexpr (VW == 4) *reinterpret_cast<uint2 *>(d) = uint2{w[0], w[1]};
             else *reinterpret_cast<unsigned *>(d) = w[0];
@@ -49,13 +50,17 @@ __device__ __forceinline__ void store_vec1(void *lvl, bool bf16, long long g, co
 // ... and to the level's line-phase shadow copy at +sh bytes when sh != 0
 // (RC_SHADOW: the same values, every store duplicated; sh is wave-uniform).
 template <int VW>
-__device__ __forceinline__ void store_vec(void *lvl, bool bf16, long long g, const float *v, long long sh) {
-    store_vec1<VW>(lvl, bf16, g, v);
-    if (sh) store_vec1<VW>(static_cast<char *>(lvl) + sh, bf16, g, v);
+__device__ __forceinline__ void store_vec(void *lvl, int ek, long long g, const float *v, long long sh) {
+    store_vec1<VW>(lvl, ek, g, v);
+    if (sh) store_vec1<VW>(static_cast<char *>(lvl) + sh, ek, g, v);
 }
 
 __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
     return (unsigned)f32_to_bf16(lo) | ((unsigned)f32_to_bf16(hi) << 16);
+}
+// ... of the element kind ek (kBF16 / kF16)
+__device__ __forceinline__ unsigned pack_h16x2(float lo, float hi, int ek) {
+    return (unsigned)f32_to_h16(lo, ek) | ((unsigned)f32_to_h16(hi, ek) << 16);
 }
 
 __device__ __forceinline__ uint32_t lds_u32(const void *p) {
@@ -80,7 +85,7 @@ __device__ __forceinline__ void lds_st1(uint32_t a, float v) {
 // lanes per row.
 template <int VW>
 __device__ __forceinline__ void store_rows16(uint32_t st, int p, int cw, void *lvl, long long ld,
-                                             bool bf16, long long rowbase, int w1_0, int col0, int W1,
+                                             int ek, long long rowbase, int w1_0, int col0, int W1,
                                              int Wl, int lane, long long sh) {
     if constexpr (VW == 1) {
         // an image wider than the wave (the bf16 ring's 80-column wave tiles
@@ -93,7 +98,7 @@ __device__ __forceinline__ void store_rows16(uint32_t st, int p, int cw, void *l
                 for (int j = lane; j < cw; j += 64) {
                     float x0;
                     asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(x0) : "v"(st + 4 * (R * p + j)));
-                    if (w1 < W1 && col0 + j < Wl) store_vec<1>(lvl, bf16, (rowbase + w1) * ld + col0 + j, &x0, sh);
+                    if (w1 < W1 && col0 + j < Wl) store_vec<1>(lvl, ek, (rowbase + w1) * ld + col0 + j, &x0, sh);
                 }
             }
             return;
@@ -128,28 +133,29 @@ __device__ __forceinline__ void store_rows16(uint32_t st, int p, int cw, void *l
             v[0] = x0;
         }
         const bool ok = Rl < rpi && R < 16 && w1 < W1 && col < Wl;
-        if (ok) store_vec<VW>(lvl, bf16, (rowbase + w1) * ld + col, v, sh);
+        if (ok) store_vec<VW>(lvl, ek, (rowbase + w1) * ld + col, v, sh);
     }
 }
 
 __device__ __forceinline__ void store_rows16_any(uint32_t st, int p, int cw, void *lvl, long long ld,
-                                                 bool bf16, long long rowbase, int w1_0, int col0,
+                                                 int ek, long long rowbase, int w1_0, int col0,
                                                  int W1, int Wl, int lane, long long sh) {
     // widest vector dividing the image width, the first column (so every
     // vector is naturally aligned) and the row stride
-    if (bf16 && ld % 8 == 0 && cw % 8 == 0 && col0 % 8 == 0)
-        store_rows16<8>(st, p, cw, lvl, ld, bf16, rowbase, w1_0, col0, W1, Wl, lane, sh);
+    if (ek && ld % 8 == 0 && cw % 8 == 0 && col0 % 8 == 0)
+        store_rows16<8>(st, p, cw, lvl, ld, ek, rowbase, w1_0, col0, W1, Wl, lane, sh);
     else if (ld % 4 == 0 && cw % 4 == 0 && col0 % 4 == 0)
-        store_rows16<4>(st, p, cw, lvl, ld, bf16, rowbase, w1_0, col0, W1, Wl, lane, sh);
+        store_rows16<4>(st, p, cw, lvl, ld, ek, rowbase, w1_0, col0, W1, Wl, lane, sh);
     else if (ld % 2 == 0 && cw % 2 == 0 && col0 % 2 == 0)
-        store_rows16<2>(st, p, cw, lvl, ld, bf16, rowbase, w1_0, col0, W1, Wl, lane, sh);
+        store_rows16<2>(st, p, cw, lvl, ld, ek, rowbase, w1_0, col0, W1, Wl, lane, sh);
     else
-        store_rows16<1>(st, p, cw, lvl, ld, bf16, rowbase, w1_0, col0, W1, Wl, lane, sh);
+        store_rows16<1>(st, p, cw, lvl, ld, ek, rowbase, w1_0, col0, W1, Wl, lane, sh);
 }
 
-__device__ __forceinline__ float pool2(float x, float y, bool bf) {
+// one pooling step; a 16-bit pyramid (ek = kBF16 / kF16) rounds it as stored
+__device__ __forceinline__ float pool2(float x, float y, int ek) {
     const float m = (x + y) * 0.5f;
-    return bf ? round_bf16(m) : m;
+    return ek ? round_h16(m, ek) : m;
 }
 
 // Rows [0, 16) of a wave's staged fp32 image of level L (CW columns, a
@@ -198,7 +204,7 @@ __device__ __forceinline__ void flush_rows16_fast(uint32_t st, const BuildArgs &
 #pragma unroll
                 for (int c = 0; c < VW; ++c) v[c] = x[k][c];
             }
-            store_vec<VW>(a.lvl[L], false, (rowbase + w1) * a.ld[L] + col, v, a.shadow[L]);
+            store_vec<VW>(a.lvl[L], kF32, (rowbase + w1) * a.ld[L] + col, v, a.shadow[L]);
         }
     }
 }
@@ -256,7 +262,7 @@ __device__ __forceinline__ void epilogue_sheared(f32x4 (&acc)[FMA][4], const Bui
         if (lv2) {
 #pragma unroll
             for (int ma = 0; ma < FMA; ++ma) {
-                const float s2 = pool2(pool2(v[ma][0], v[ma][1], false), pool2(v[ma][2], v[ma][3], false), false);
+                const float s2 = pool2(pool2(v[ma][0], v[ma][1], kF32), pool2(v[ma][2], v[ma][3], kF32), kF32);
                 lds_st1(st0 + S2OFF + 4 * (i * P2 + 4 * ma + g), s2);
             }
         }
@@ -328,12 +334,13 @@ __device__ __forceinline__ void epilogue_sheared(f32x4 (&acc)[FMA][4], const Bui
 // w1_end: rows (w1) at or past it are not stored -- the image edge, or the
 // end of this wave's block when it covers fewer than 4 fragments of w1 inside
 // a tile (split kernel, volume_split.hip); -1 = a.W1.
-template <int FMA, int MODE, int NLM>
+// EK: the element kind a 16-bit pyramid (a.pyr_bf16 != 0) holds in this kernel.
+template <int FMA, int MODE, int NLM, int EK = kBF16>
 __device__ __forceinline__ void epilogue_swapped(f32x4 (&acc)[FMA][4], const BuildArgs &a, int row,
                                                  int m0, int n0, int lane0, uint32_t st0, int w1_end = -1) {
     const int w1e = w1_end < 0 || w1_end > a.W1 ? a.W1 : w1_end;
     constexpr int WT = 16 * FMA;
-    const bool bf = a.pyr_bf16 != 0;
+    const int bf = a.pyr_bf16 != 0 ? EK : kF32;
     // kModeL2Stores (dev timing only, wrong output): every row stores into
     // one of 8 rows, so the same instructions write L2-resident lines
     const long long rowbase = (long long)((MODE & kModeL2Stores) ? (row & 7) : row) * a.W1;
@@ -364,8 +371,8 @@ __device__ __forceinline__ void epilogue_swapped(f32x4 (&acc)[FMA][4], const Bui
                 float u[FMA][2];
 #pragma unroll
                 for (int ma = 0; ma < FMA; ++ma) {
-                    u[ma][0] = pool2(v[ma][0], v[ma][1], false);
-                    u[ma][1] = pool2(v[ma][2], v[ma][3], false);
+                    u[ma][0] = pool2(v[ma][0], v[ma][1], kF32);
+                    u[ma][1] = pool2(v[ma][2], v[ma][3], kF32);
                 }
                 if (a.lvl[1]) {
 #pragma unroll
@@ -376,7 +383,7 @@ __device__ __forceinline__ void epilogue_swapped(f32x4 (&acc)[FMA][4], const Bui
                 if (nl < 3) continue;
                 float s2[FMA];
 #pragma unroll
-                for (int ma = 0; ma < FMA; ++ma) s2[ma] = pool2(u[ma][0], u[ma][1], false);
+                for (int ma = 0; ma < FMA; ++ma) s2[ma] = pool2(u[ma][0], u[ma][1], kF32);
                 if (a.lvl[2]) {
 #pragma unroll
                     for (int ma = 0; ma < FMA; ++ma) lds_st1(st0 + 4 * (i * (WT / 4 + 4) + 4 * ma + g), s2[ma]);
@@ -389,7 +396,7 @@ __device__ __forceinline__ void epilogue_swapped(f32x4 (&acc)[FMA][4], const Bui
 #pragma unroll
                     for (int ma = 0; ma < FMA; ++ma) {
                         const float o = __shfl_xor(s2[ma], 16);
-                        s3[ma] = (g & 1) ? pool2(o, s2[ma], false) : pool2(s2[ma], o, false);
+                        s3[ma] = (g & 1) ? pool2(o, s2[ma], kF32) : pool2(s2[ma], o, kF32);
                     }
                     if (a.lvl[3]) {
                         if (!(g & 1)) {
@@ -405,7 +412,7 @@ __device__ __forceinline__ void epilogue_swapped(f32x4 (&acc)[FMA][4], const Bui
 #pragma unroll
                         for (int ma = 0; ma < FMA; ++ma) {
                             const float o = __shfl_xor(s3[ma], 32);
-                            s4[ma] = (g & 2) ? pool2(o, s3[ma], false) : pool2(s3[ma], o, false);
+                            s4[ma] = (g & 2) ? pool2(o, s3[ma], kF32) : pool2(s3[ma], o, kF32);
                         }
                         if (a.lvl[4]) {
                             if (g == 0) {
@@ -444,7 +451,7 @@ __device__ __forceinline__ void epilogue_swapped(f32x4 (&acc)[FMA][4], const Bui
             apply_scale(v[ma], a);
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                if (bf) v[ma][r] = round_bf16(v[ma][r]);
+                if (bf) v[ma][r] = round_h16(v[ma][r], bf);
             acc[ma][0] = acc[ma][1];
             acc[ma][1] = acc[ma][2];
             acc[ma][2] = acc[ma][3];

@@ -33,13 +33,15 @@ __device__ __forceinline__ float pixel_x(const LookupArgs &a, long long bimg, lo
     return x;
 }
 
-template <int R, bool BF16>
+// EK: the pyramid's element kind (kF32 / kBF16 / kF16; a kernel's `bool BF16`
+// converts to the first two).
+template <int R, int EK>
 struct LevelWindow {
     static constexpr int T = 2 * R + 1;
     static constexpr int NW = 2 * R + 4;              // window elements
-    static constexpr int EPV = BF16 ? 8 : 4;          // elements per 16-B load
+    static constexpr int EPV = EK != kF32 ? 8 : 4;    // elements per 16-B load
     static constexpr int NV = (NW + 2 * (EPV - 1)) / EPV;
-    static constexpr int ES = BF16 ? 2 : 4;
+    static constexpr int ES = EK != kF32 ? 2 : 4;
     uint32_t q[NV][4];                                 // raw loaded dwords
     float xp[T];
     float n;
@@ -47,10 +49,10 @@ struct LevelWindow {
     bool inwin;
 };
 
-template <int R, bool BF16, bool EXACT>
-__device__ __forceinline__ void issue_level(LevelWindow<R, BF16> &lw, const LookupArgs &a, int i,
+template <int R, int EK, bool EXACT>
+__device__ __forceinline__ void issue_level(LevelWindow<R, EK> &lw, const LookupArgs &a, int i,
                                             float x, long long pblk, long long lrow) {
-    typedef LevelWindow<R, BF16> LW;
+    typedef LevelWindow<R, EK> LW;
     const int W = a.W[i];
     const long long ld = a.ld[i];
     const float Wm1 = (float)(W - 1);
@@ -89,10 +91,10 @@ __device__ __forceinline__ void issue_level(LevelWindow<R, BF16> &lw, const Look
     }
 }
 
-template <int R, bool BF16, class Sink>
-__device__ __forceinline__ void finish_level(const LevelWindow<R, BF16> &lw, const LookupArgs &a,
+template <int R, int EK, class Sink>
+__device__ __forceinline__ void finish_level(const LevelWindow<R, EK> &lw, const LookupArgs &a,
                                              int i, long long pblk, long long lrow, Sink &&sink) {
-    typedef LevelWindow<R, BF16> LW;
+    typedef LevelWindow<R, EK> LW;
     constexpr int T = LW::T, NW = LW::NW, EPV = LW::EPV, NE = LW::NV * EPV;
     const int W = a.W[i];
     const float Wm1 = (float)(W - 1);
@@ -102,9 +104,9 @@ __device__ __forceinline__ void finish_level(const LevelWindow<R, BF16> &lw, con
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const uint32_t u = lw.q[k][c];
-            if constexpr (BF16) {
-                v[k * 8 + 2 * c] = __builtin_bit_cast(float, u << 16);
-                v[k * 8 + 2 * c + 1] = __builtin_bit_cast(float, u & 0xFFFF0000u);
+            if constexpr (EK != kF32) {
+                v[k * 8 + 2 * c] = h16_lo(u, EK);
+                v[k * 8 + 2 * c + 1] = h16_hi(u, EK);
             } else {
                 v[k * 4 + c] = __builtin_bit_cast(float, u);
             }
@@ -149,10 +151,10 @@ __device__ __forceinline__ void finish_level(const LevelWindow<R, BF16> &lw, con
             const bool ok1 = (x0 + 1.0f >= 0.0f) && (x0 + 1.0f <= Wm1);
             const long long k0 = lrow * a.ld[i] + (long long)x0;
             float v0 = 0.0f, v1 = 0.0f;
-            if constexpr (BF16) {
+            if constexpr (EK != kF32) {
                 const uint16_t *rowp = reinterpret_cast<const uint16_t *>(base);
-                if (ok0) v0 = bf16_to_f32(rowp[k0]);
-                if (ok1) v1 = bf16_to_f32(rowp[k0 + 1]);
+                if (ok0) v0 = h16_to_f32(rowp[k0], EK);
+                if (ok1) v1 = h16_to_f32(rowp[k0 + 1], EK);
             } else {
                 const float *rowp = reinterpret_cast<const float *>(base);
                 if (ok0) v0 = rowp[k0];

@@ -2,7 +2,8 @@
 // major lookup_sheared_pair_kernel and lookup_records_kernel, with the span
 // helpers they share.  Templates only: lookup.hip instantiates the fp32-output
 // kernels, lookup_half.hip the fp16 / bf16-output ones (RC_OUT_F16 /
-// RC_OUT_BF16), so neither translation unit pays for the other's compile.
+// RC_OUT_BF16), lookup_f16pyr.hip the ones that read an fp16 pyramid
+// (RC_F16), so no translation unit pays for another's compile.
 #pragma once
 #include <type_traits>
 
@@ -61,12 +62,14 @@ __device__ __forceinline__ float derived_elem(const float *row1, long long k) {
 // 16 16-B loads per lane, and with fewer selects.  Window elements outside
 // [0, W_level) are zeroed once per level, which is exactly the reference's
 // per-tap zero padding (a tap reads window elements x0 and x0+1 only).
-template <int R, bool BF16 = false>
+// EK: the pyramid's element kind (kF32 / kBF16 / kF16; a kernel's `bool BF16`
+// converts to the first two) -- here and in every helper below.
+template <int R, int EK = kF32>
 struct PairSpan {
     static constexpr int NW = 2 * R + 4;              // window elements per level
     static constexpr int NS = 2 * NW;                 // span elements
-    static constexpr int EPC = BF16 ? 8 : 4;          // elements per 16-B chunk
-    static constexpr int ES = BF16 ? 2 : 4;           // element bytes
+    static constexpr int EPC = EK != kF32 ? 8 : 4;    // elements per 16-B chunk
+    static constexpr int ES = EK != kF32 ? 2 : 4;     // element bytes
     // the span starts at an even element: misaligned by 0, 2, .., EPC-2
     static constexpr int NC = (NS + EPC - 2 + EPC - 1) / EPC;
     uint32_t q[NC][4];                                // raw chunks
@@ -76,9 +79,9 @@ struct PairSpan {
     bool inwin, valid;
     // element e of the loaded chunks, as fp32
     __device__ __forceinline__ float elem(int e) const {
-        if constexpr (BF16) {
+        if constexpr (EK != kF32) {
             const uint32_t u = q[e >> 3][(e & 7) >> 1];
-            return __builtin_bit_cast(float, (e & 1) ? (u & 0xFFFF0000u) : (u << 16));
+            return (e & 1) ? h16_hi(u, EK) : h16_lo(u, EK);
         } else {
             return __builtin_bit_cast(float, q[e >> 2][e & 3]);
         }
@@ -109,8 +112,8 @@ __device__ __forceinline__ float tap_xp(float xl, int k, const LevelConsts &c) {
 // (clipped to the rows; empty as lo_e > hi_e).  The x' of each level's two
 // edge taps, which bound that range, are kept in ps.xe: window_taps takes
 // them from there instead of evaluating them again.
-template <int R, bool BF16>
-__device__ __forceinline__ void plan_pair(PairSpan<R, BF16> &ps, const LookupArgs &a, int lo, float x,
+template <int R, int EK>
+__device__ __forceinline__ void plan_pair(PairSpan<R, EK> &ps, const LookupArgs &a, int lo, float x,
                                           int &lo_e, int &hi_e) {
     const int Wlo = a.W[lo], Whi = a.W[lo + 1];
     const float xlo = x / (float)(1 << lo), xhi = x / (float)(2 << lo);
@@ -138,18 +141,18 @@ __device__ __forceinline__ void plan_pair(PairSpan<R, BF16> &ps, const LookupArg
 
 // The loads of one pair's span: the buffer resource and the byte offset of
 // each 16-B chunk (an out-of-range offset where the taps read none of it).
-template <int R, bool BF16>
+template <int R, int EK>
 struct PairLoads {
     __amdgpu_buffer_rsrc_t rs;
-    int off[PairSpan<R, BF16>::NC];
+    int off[PairSpan<R, EK>::NC];
 };
 
-template <int R, bool BF16 = false>
-__device__ __forceinline__ PairLoads<R, BF16> plan_pair_loads(PairSpan<R, BF16> &ps, const LookupArgs &a, int lo,
+template <int R, int EK = kF32>
+__device__ __forceinline__ PairLoads<R, EK> plan_pair_loads(PairSpan<R, EK> &ps, const LookupArgs &a, int lo,
                                                               float x, long long pblk, long long lrow) {
-    typedef PairSpan<R, BF16> PS;
+    typedef PairSpan<R, EK> PS;
     int lo_e, hi_e;
-    plan_pair<R, BF16>(ps, a, lo, x, lo_e, hi_e);
+    plan_pair<R, EK>(ps, a, lo, x, lo_e, hi_e);
     const int sa = 2 * ((int)ps.m - R - 1);
     const int ea = sa & ~(PS::EPC - 1);
     ps.sh = sa - ea;
@@ -159,7 +162,7 @@ __device__ __forceinline__ PairLoads<R, BF16> plan_pair_loads(PairSpan<R, BF16> 
     // line; each lane reads its span from the copy in which it touches fewer
     // lines (same values either way).  The resource then spans both copies.
     const long long shb = a.shadow[lo];
-    PairLoads<R, BF16> pl;
+    PairLoads<R, EK> pl;
     pl.rs = make_rsrc(lvl + pblk * ld * PS::ES, clamp_bytes((a.P - pblk) * ld * PS::ES + shb));
     uint32_t phase = 0;
     if (shb != 0 && lo_e <= hi_e) {
@@ -182,10 +185,10 @@ __device__ __forceinline__ PairLoads<R, BF16> plan_pair_loads(PairSpan<R, BF16> 
     return pl;
 }
 
-template <int R, bool BF16>
-__device__ __forceinline__ void load_pair(PairSpan<R, BF16> &ps, const PairLoads<R, BF16> &pl) {
+template <int R, int EK>
+__device__ __forceinline__ void load_pair(PairSpan<R, EK> &ps, const PairLoads<R, EK> &pl) {
 #pragma unroll
-    for (int k = 0; k < PairSpan<R, BF16>::NC; ++k) {
+    for (int k = 0; k < PairSpan<R, EK>::NC; ++k) {
         const auto v = __builtin_amdgcn_raw_buffer_load_b128(pl.rs, pl.off[k], 0, 0);
 #pragma unroll
         for (int c = 0; c < 4; ++c) ps.q[k][c] = v[c];
@@ -234,19 +237,19 @@ __device__ __forceinline__ void window_taps(const float *w, float xl, float nwin
 // The memory path for a lane whose level pair breaks the span relation
 // n = 2m + dd (only a subnormal x can): every tap re-read, level-i element k
 // = pool of S consecutive span-level elements.
-// level-i element k (S consecutive bf16 span-level elements, each level of
-// the chain rounded to bf16 as stored)
-template <int S>
-__device__ __forceinline__ float derived_elem_bf16(const uint16_t *row, long long k) {
+// level-i element k (S consecutive 16-bit span-level elements of kind EK,
+// each level of the chain rounded to that kind as stored)
+template <int S, int EK>
+__device__ __forceinline__ float derived_elem_h16(const uint16_t *row, long long k) {
     if constexpr (S == 1) {
-        return bf16_to_f32(row[k]);
+        return h16_to_f32(row[k], EK);
     } else {
-        const float a = derived_elem_bf16<S / 2>(row, 2 * k), b = derived_elem_bf16<S / 2>(row, 2 * k + 1);
-        return round_bf16((a + b) * 0.5f);
+        const float a = derived_elem_h16<S / 2, EK>(row, 2 * k), b = derived_elem_h16<S / 2, EK>(row, 2 * k + 1);
+        return round_h16((a + b) * 0.5f, EK);
     }
 }
 
-template <int R, int S, bool BF16 = false>
+template <int R, int S, int EK = kF32>
 __device__ __forceinline__ void level_taps_mem(const void *rowv, float xl, const LevelConsts &lc, float *res) {
     constexpr int T = 2 * R + 1;
     const float Wm1 = lc.Wm1;
@@ -257,10 +260,10 @@ __device__ __forceinline__ void level_taps_mem(const void *rowv, float xl, const
         const bool ok0 = (x0 >= 0.0f) && (x0 <= Wm1);
         const bool ok1 = (x0 + 1.0f >= 0.0f) && (x0 + 1.0f <= Wm1);
         float v0 = 0.0f, v1 = 0.0f;
-        if constexpr (BF16) {
+        if constexpr (EK != kF32) {
             const uint16_t *row = static_cast<const uint16_t *>(rowv);
-            if (ok0) v0 = derived_elem_bf16<S>(row, (long long)x0);
-            if (ok1) v1 = derived_elem_bf16<S>(row, (long long)x0 + 1);
+            if (ok0) v0 = derived_elem_h16<S, EK>(row, (long long)x0);
+            if (ok1) v1 = derived_elem_h16<S, EK>(row, (long long)x0 + 1);
         } else {
             const float *row = static_cast<const float *>(rowv);
             if (ok0) v0 = derived_elem<S>(row, (long long)x0);
@@ -273,9 +276,9 @@ __device__ __forceinline__ void level_taps_mem(const void *rowv, float xl, const
 // The span's elements from its loaded chunks: span element j = chunk element
 // j + sh, sh in {0, 2, .., EPC-2}.  This consumes the chunks: after it their
 // registers are free for the next span's loads.
-template <int R, bool BF16>
-__device__ __forceinline__ void span_shift(const PairSpan<R, BF16> &ps, float *s) {
-    typedef PairSpan<R, BF16> PS;
+template <int R, int EK>
+__device__ __forceinline__ void span_shift(const PairSpan<R, EK> &ps, float *s) {
+    typedef PairSpan<R, EK> PS;
 #pragma unroll
     for (int j = 0; j < PS::NS; ++j) {
         float v = ps.elem(j);
@@ -289,10 +292,10 @@ __device__ __forceinline__ void span_shift(const PairSpan<R, BF16> &ps, float *s
 // Both levels of a pair from its span s[NS]: the two windows (after which
 // the span is dead), then the even level's taps and stores, then the odd
 // level's, so that one level's x' and results are live at a time.
-template <int R, bool NOFALLBACK = false, bool BF16 = false, class Sink, class Mid>
-__device__ __forceinline__ void finish_span(const PairSpan<R, BF16> &ps, const float *s, const LookupArgs &a,
+template <int R, bool NOFALLBACK = false, int EK = kF32, class Sink, class Mid>
+__device__ __forceinline__ void finish_span(const PairSpan<R, EK> &ps, const float *s, const LookupArgs &a,
                                             int lo, float x, long long pp, Sink &&sink, Mid &&mid) {
-    typedef PairSpan<R, BF16> PS;
+    typedef PairSpan<R, EK> PS;
     constexpr int T = 2 * R + 1, NW = PS::NW;
     const int Wlo = a.W[lo], Whi = a.W[lo + 1];
     const int mi = (int)ps.m - R - 1, ni = (int)ps.n - R - 1;
@@ -304,7 +307,7 @@ __device__ __forceinline__ void finish_span(const PairSpan<R, BF16> &ps, const f
 #pragma unroll
     for (int jj = 0; jj < NW; ++jj) {
         float pm = (s[2 * jj] + s[2 * jj + 1]) * 0.5f;      // model.py:294 in fp32
-        if constexpr (BF16) pm = round_bf16(pm);           // the odd level as stored
+        if constexpr (EK != kF32) pm = round_h16(pm, EK);  // the odd level as stored
         wodd[jj] = (unsigned)(mi + jj) < (unsigned)Whi ? pm : 0.0f;
         const float e = dd == 0 ? s[R + 1 + jj] : s[R + 2 + jj];
         weven[jj] = (unsigned)(ni + jj) < (unsigned)Wlo ? e : 0.0f;
@@ -312,22 +315,22 @@ __device__ __forceinline__ void finish_span(const PairSpan<R, BF16> &ps, const f
     const LevelConsts clo = level_consts(a, lo), chi = level_consts(a, lo + 1);
     float r[T];
     window_taps<R>(weven, xlo, ps.n, clo, ps.xe[0], ps.xe[1], r);
-    if (__builtin_expect(mem, 0)) level_taps_mem<R, 1, BF16>(row, xlo, clo, r);
+    if (__builtin_expect(mem, 0)) level_taps_mem<R, 1, EK>(row, xlo, clo, r);
 #pragma unroll
     for (int t = 0; t < T; ++t) sink(lo * T + t, r[t]);
     mid();
     window_taps<R>(wodd, xhi, ps.m, chi, ps.xe[2], ps.xe[3], r);
-    if (__builtin_expect(mem, 0)) level_taps_mem<R, 2, BF16>(row, xhi, chi, r);
+    if (__builtin_expect(mem, 0)) level_taps_mem<R, 2, EK>(row, xhi, chi, r);
 #pragma unroll
     for (int t = 0; t < T; ++t) sink((lo + 1) * T + t, r[t]);
 }
 
-template <int R, bool NOFALLBACK = false, bool BF16 = false, class Sink>
-__device__ __forceinline__ void finish_pair(const PairSpan<R, BF16> &ps, const LookupArgs &a, int lo,
+template <int R, bool NOFALLBACK = false, int EK = kF32, class Sink>
+__device__ __forceinline__ void finish_pair(const PairSpan<R, EK> &ps, const LookupArgs &a, int lo,
                                             float x, long long pp, Sink &&sink) {
-    float s[PairSpan<R, BF16>::NS];
-    span_shift<R, BF16>(ps, s);
-    finish_span<R, NOFALLBACK, BF16>(ps, s, a, lo, x, pp, sink, [] {});
+    float s[PairSpan<R, EK>::NS];
+    span_shift<R, EK>(ps, s);
+    finish_span<R, NOFALLBACK, EK>(ps, s, a, lo, x, pp, sink, [] {});
 }
 
 // One lane's pixel of one group: index, x, output offset (elements of a.out,
@@ -380,8 +383,11 @@ __device__ __forceinline__ PairPixel pair_pixel(const LookupArgs &a, long long p
 // depend on it: the fp32 value that is rounded is the fp32 kernel's.  NCHW:
 // one 2-byte store per lane and channel plane (a 128-B run per wave; plane
 // bases are only 2-byte aligned when H*W1 is odd, so nothing wider).
-template <int R, int NL, int M = 0, bool BF16 = false, int WPE = 1, bool CL = false, class OT = float>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void lookup_pair_kernel(LookupArgs a) {
+// The kernel's body is lookup_pair_body (EK: the pyramid's element kind):
+// lookup_pair_kernel wraps it for fp32 and bf16 pyramids, lookup_f16pyr.hip
+// for fp16 ones under a name of its own.
+template <int R, int NL, int M, int EK, bool CL, class OT>
+__device__ __forceinline__ void lookup_pair_body(const LookupArgs &a) {
     static_assert(NL == 2 || NL == 4, "pair lookup: 2 or 4 levels");
     constexpr int NP = NL / 2;                        // spans per pixel
     // XCD-contiguous block order: neighbouring pixel blocks, whose output
@@ -390,15 +396,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     const int blk = M == 5 ? (int)blockIdx.x : xcd_remap(blockIdx.x, gridDim.x);
     const PairPixel q = pair_pixel<R, NL>(a, (long long)blk * 256);
     OT *const outp = reinterpret_cast<OT *>(a.out) + q.ooff;
-    PairSpan<R, BF16> sp[NP];
+    PairSpan<R, EK> sp[NP];
     // The load schedule, pinned: the first span's loads go
     // out before the second span's address math; the second span's loads go
     // out between the two levels of the first (see below).
-    PairLoads<R, BF16> pl[NP];
-    pl[0] = plan_pair_loads<R, BF16>(sp[0], a, 0, q.x, q.pblk, q.lrow);
-    load_pair<R, BF16>(sp[0], pl[0]);
+    PairLoads<R, EK> pl[NP];
+    pl[0] = plan_pair_loads<R, EK>(sp[0], a, 0, q.x, q.pblk, q.lrow);
+    load_pair<R, EK>(sp[0], pl[0]);
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (NP > 1) pl[1] = plan_pair_loads<R, BF16>(sp[1], a, 2, q.x, q.pblk, q.lrow);
+    if constexpr (NP > 1) pl[1] = plan_pair_loads<R, EK>(sp[1], a, 2, q.x, q.pblk, q.lrow);
     constexpr int C = NL * (2 * R + 1);
     // CL: channels-last output (RC_OUT_CHANNELS_LAST), out[p*C + ch].  A
     // wave's 64 pixels own one contiguous run of 64*C elements; it is gathered
@@ -417,8 +423,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     };
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
-        float s[PairSpan<R, BF16>::NS];
-        span_shift<R, BF16>(sp[k], s);
+        float s[PairSpan<R, EK>::NS];
+        span_shift<R, EK>(sp[k], s);
         // The next span's loads: after this span's even level is done and
         // stored, before its odd level.  By then the shift has consumed this
         // span's chunks and the even level's window and x' are dead, so the
@@ -429,12 +435,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
             if constexpr (NP > 1) {
                 if (k == 0) {
                     __builtin_amdgcn_sched_barrier(0);
-                    load_pair<R, BF16>(sp[1], pl[1]);
+                    load_pair<R, EK>(sp[1], pl[1]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
         };
-        finish_span<R, M == 2, BF16>(sp[k], s, a, 2 * k, q.x, q.pp, sink, next);
+        finish_span<R, M == 2, EK>(sp[k], s, a, 2 * k, q.x, q.pp, sink, next);
         __builtin_amdgcn_sched_barrier(0);
     }
     if constexpr (TILE) {
@@ -463,6 +469,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
             }
         }
     }
+}
+
+template <int R, int NL, int M = 0, bool BF16 = false, int WPE = 1, bool CL = false, class OT = float>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void lookup_pair_kernel(LookupArgs a) {
+    lookup_pair_body<R, NL, M, BF16 ? kBF16 : kF32, CL, OT>(a);
 }
 
 // finish_pair's memory path over the disparity-major layout: every tap of

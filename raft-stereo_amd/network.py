@@ -233,7 +233,8 @@ class BasicMultiUpdateBlock(nn.Module):
 class RAFTStereo(nn.Module):
     """model.py:335-383 with the correlation block pluggable (``corr_block``)."""
 
-    def __init__(self, args, corr_block=None, fuse_convc1=False, fuse_step=False, corr_out_dtype=None):
+    def __init__(self, args, corr_block=None, fuse_convc1=False, fuse_step=False, corr_out_dtype=None,
+                 corr_pyramid_dtype=None):
         super().__init__()
         self.args = args
         # corr_out_dtype (DESIGN.md §3.2j): the lookup output's dtype (with
@@ -246,6 +247,18 @@ class RAFTStereo(nn.Module):
                 or isinstance(corr_out_dtype, torch.dtype)):
             raise ValueError(f"RAFTStereo: corr_out_dtype={corr_out_dtype!r}: None, 'autocast' or a torch.dtype")
         self.corr_out_dtype = corr_out_dtype
+        # corr_pyramid_dtype: the corr block's pyramid_dtype.
+        # None: the block's own default (a bf16 pyramid for fp16 / bf16 fmaps).
+        # "autocast": the autocast dtype when args.mixed_precision runs on a
+        # GPU -- under fp16 autocast the encoders' fp16 fmaps then feed the
+        # fp16 MFMA build as they are and the pyramid keeps their 11
+        # significant bits (overflow above 65504 stores +-inf); nothing
+        # otherwise.  A torch.dtype is passed to the corr block as it is.
+        if not (corr_pyramid_dtype is None or corr_pyramid_dtype == "autocast"
+                or isinstance(corr_pyramid_dtype, torch.dtype)):
+            raise ValueError(f"RAFTStereo: corr_pyramid_dtype={corr_pyramid_dtype!r}: None, 'autocast' or a "
+                             "torch.dtype")
+        self.corr_pyramid_dtype = corr_pyramid_dtype
         context_dims = args.hidden_dims
         self.cnet = BasicEncoder(output_dim=[args.hidden_dims, context_dims], norm_fn="batch",
                                  downsample=args.n_downsample)
@@ -273,13 +286,17 @@ class RAFTStereo(nn.Module):
         return torch.autocast(dev, dtype=dtype, enabled=enabled and dev == "cuda")
 
     def _corr_kwargs(self):
-        """The out_dtype keyword for the corr block -- only when the option is
-        set, so a ``corr_block`` with the reference's signature keeps working."""
-        od = self.corr_out_dtype
-        if od == "autocast":
-            on = bool(self.args.mixed_precision) and torch.cuda.is_available()
-            od = getattr(self.args, "autocast_dtype", torch.float16) if on else None
-        return {} if od is None else {"out_dtype": od}
+        """The out_dtype / pyramid_dtype keywords for the corr block -- each only
+        when its option is set, so a ``corr_block`` with the reference's
+        signature keeps working."""
+        on = bool(self.args.mixed_precision) and torch.cuda.is_available()
+        auto = getattr(self.args, "autocast_dtype", torch.float16) if on else None
+        od = auto if self.corr_out_dtype == "autocast" else self.corr_out_dtype
+        pd = auto if self.corr_pyramid_dtype == "autocast" else self.corr_pyramid_dtype
+        kw = {} if od is None else {"out_dtype": od}
+        if pd is not None:
+            kw["pyramid_dtype"] = pd
+        return kw
 
     def features(self, image1, image2):
         """Encoders (stay on PyTorch ops): fmaps for the corr path + GRU state."""
@@ -328,7 +345,8 @@ class RAFTStereo(nn.Module):
                     # corr_out_dtype: the fused kernel writes what convc2 reads
                     # under autocast (the keyword only when the option is set)
                     corr = corr_fn.lookup_convc1(coords1, enc.convc1.weight, enc.convc1.bias,
-                                                 differentiable=torch.is_grad_enabled(), **corr_kw)
+                                                 differentiable=torch.is_grad_enabled(),
+                                                 **{k: v for k, v in corr_kw.items() if k == "out_dtype"})
                 else:
                     corr = corr_fn(coords1)             # the hot path, every iteration
                 flow = coords1 - coords0
