@@ -235,7 +235,14 @@ int rc_corr_pool(const void *in, long ld_in, void *out, long ld_out, long rows,
  *          coords_x[b*coord_batch_stride + h*W1 + w] (the y channel is
  *          ignored, model.py:299/:308).
  *   out:   [B][levels*(2*radius+1)][H][W1] fp32, channel = level*(2r+1)+(t+r).
- *   radius in 1..8, levels in 1..RC_MAX_LEVELS. */
+ *   radius in 1..8, levels in 1..RC_MAX_LEVELS.
+ *   A level of width 1 is accepted, here and by every entry point that
+ *   samples a pyramid: the sampler normalises by widths[i] - 1 = 0
+ *   (model.py:271), so every tap of that level is NaN at every x, finite or
+ *   not, exactly as the reference's arithmetic gives (the tap weights are
+ *   NaN, so the zero-padding short cuts for far-away x do not show).  The
+ *   reference itself never looks such a level up: its pyramid has
+ *   num_levels + 1 levels, so level num_levels - 1 is at least 2 wide. */
 int rc_corr_lookup(const void *const *pyr, const int *widths, const long *pyr_ld,
                    int pyr_dtype, int levels, int radius, const float *coords_x,
                    long coord_batch_stride, int B, int H, int W1, float *out,

@@ -1,5 +1,6 @@
 """Guarded arena and raw C-ABI callers for the volume sweeps
-(test_volume_sweep_gpu.py, test_volume_sweep_host.py).
+(test_volume_sweep_gpu.py, test_volume_sweep_host.py) and, through
+lookup_sweep_util.py, the lookup sweeps.
 
 ``arena`` carves every operand and output of one kernel call out of a single
 buffer filled with a NaN bit pattern, at 16-byte-aligned addresses that are
@@ -46,11 +47,14 @@ def bound(sizes):
 
 class Arena:
     """specs: list of (name, nbytes, data) -- data a contiguous CPU tensor of
-    nbytes bytes for an input, None for an output region."""
+    nbytes bytes for an input, None for an output region -- or of (name,
+    nbytes, data, True) for an in/out region: initial data that the call may
+    change (an accumulating gradient buffer, coords updated in place)."""
 
     def __init__(self, dev, specs, phase=0, bf16=False):
         self.sent = (SENT16 << 16 | SENT16) if bf16 else SENT32
-        sizes = [n for _, n, _ in specs]
+        specs = [(*s, False)[:4] for s in specs]
+        sizes = [s[1] for s in specs]
         self.buf = torch.empty((bound(sizes) // 4 + 1,), dtype=torch.int32, device=dev)
         self.base = self.buf.data_ptr()
         offs, self.total = plan(sizes, self.base, phase)
@@ -58,11 +62,12 @@ class Arena:
         self.off, self.size, self.outputs = {}, {}, []
         image = torch.full((self.buf.numel(),), self.sent, dtype=torch.int32)
         u8 = image.view(torch.uint8)
-        for (name, n, data), off in zip(specs, offs):
+        for (name, n, data, inout), off in zip(specs, offs):
             self.off[name], self.size[name] = off, n
-            if data is None:
+            assert data is not None or not inout, name
+            if data is None or inout:
                 self.outputs.append(name)
-            else:
+            if data is not None:
                 src = data.contiguous().reshape(-1).view(torch.uint8)
                 assert src.numel() == n, (name, src.numel(), n)
                 u8[off:off + n].copy_(src)
@@ -105,6 +110,22 @@ class Arena:
                    f"guard overwritten {dist} bytes {where} {near}")
             raise AssertionError(f"{msg} ({bad.size} bytes differ)")
 
+    def assert_outputs_written(self, names, es=4):
+        """No element (of es bytes) of the output regions ``names`` still
+        holds the sentinel: the comparisons treat NaN == NaN, so an element
+        the kernel never wrote would pass wherever the reference is NaN.  (No
+        kernel produces the sentinel's payload: the hardware's own NaNs are
+        0x7FC00000 / 0x7FC0 / 0x7E00, and a propagated input NaN would have to
+        come from the poisoned padding, which must not be read.)"""
+        for name in names:
+            assert name in self.outputs, f"{name} is not an output region"
+            if es == 2:
+                left = np.flatnonzero(self.region(name, np.uint16) == SENT16)
+            else:
+                left = np.flatnonzero(self.region(name, np.uint32) == np.uint32(self.sent))
+            assert not left.size, (f"output {name}: {left.size} of {self.size[name] // es} elements never "
+                                   f"written, the first at index {int(left[0])}")
+
 
 def arena(dev, specs, phase=0, bf16=False):
     return Arena(dev, specs, phase, bf16)
@@ -112,6 +133,31 @@ def arena(dev, specs, phase=0, bf16=False):
 
 def bf16_to_f32(u16):
     return (u16.astype(np.uint32) << 16).view(np.float32)
+
+
+def bf16_pool_np(level):
+    """avg_pool2d([1,2]) of a bf16 level in fp32, rounded to bf16 (RNE), as
+    PyTorch computes it on bf16 tensors."""
+    t = torch.from_numpy(np.ascontiguousarray(level)).bfloat16().float()
+    Wo = t.shape[1] // 2
+    pm = (t[:, 0:2 * Wo:2] + t[:, 1:2 * Wo:2]) * 0.5
+    return pm.bfloat16().float().numpy()
+
+
+def f16_pool_np(level):
+    """One pooling step of an fp16 level (given widened to fp32): the mean in
+    fp32, rounded to fp16 (nearest even), widened again."""
+    lv = np.asarray(level, np.float32)
+    Wo = lv.shape[1] // 2
+    with np.errstate(invalid="ignore", over="ignore"):
+        pm = (lv[:, 0:2 * Wo:2] + lv[:, 1:2 * Wo:2]) * np.float32(0.5)
+        return pm.astype(np.float16).astype(np.float32)
+
+
+def integer_sweep(W2):
+    """Every integer x from -40 to W2 + 40 with both fp32 neighbours."""
+    k = np.arange(-40, W2 + 41, dtype=np.float32)
+    return np.concatenate([k, np.nextafter(k, np.float32(np.inf)), np.nextafter(k, np.float32(-np.inf))])
 
 
 def _es(dt):
@@ -192,7 +238,7 @@ def guarded_sheared(dev, f1, f2, num_levels, phase=0):
     specs = [("f1", f1.numel() * 4, f1), ("f2", f2.numel() * 4, f2)] + [(f"s{l}", n[l] * 4, None) for l in keep]
     ar = arena(dev, specs, phase)
     nbuf = 3 if num_levels == 4 else 1
-    ptrs = [ar.ptr("s0"), None, ar.ptr("s2")][:nbuf]
+    ptrs = [ar.ptr(f"s{l}") if l in keep else None for l in range(nbuf)]
     rc = _lib.lib().rc_corr_build(
         ar.ptr("f1"), ar.ptr("f2"), _lib.RC_F32, B, D, H, W1, W2, _lib.ptr_array(ptrs),
         _lib.long_array([ld, W2 >> 1, ld][:nbuf]), nbuf, _lib.RC_F32 | _lib.RC_LAYOUT_DISPARITY, None)

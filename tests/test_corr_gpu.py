@@ -17,6 +17,7 @@ from oracle import coracle
 from raft_stereo_amd import CorrBlock1D
 from raft_stereo_amd import _lib
 from raft_stereo_amd import corr as rcorr
+from sweep_util import bf16_pool_np  # noqa: F401  (other test modules import it from here)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -231,15 +232,6 @@ def test_chain_not_used_for_other_levels():
         assert not CorrBlock1D(f, f, num_levels=1)._chain
         assert not CorrBlock1D(f, f, num_levels=5, radius=2)._chain
         assert not CorrBlock1D(f, f, num_levels=4, radius=5)._chain
-
-
-def bf16_pool_np(level):
-    """avg_pool2d([1,2]) of a bf16 level in fp32, rounded to bf16 (RNE), as
-    PyTorch computes it on bf16 tensors."""
-    t = torch.from_numpy(np.ascontiguousarray(level)).bfloat16().float()
-    Wo = t.shape[1] // 2
-    pm = (t[:, 0:2 * Wo:2] + t[:, 1:2 * Wo:2]) * 0.5
-    return pm.bfloat16().float().numpy()
 
 
 BF16_PAIR_SHAPES = [

@@ -20,6 +20,7 @@ from oracle import coracle
 from raft_stereo_amd import CorrBlock1D
 from raft_stereo_amd import corr as rcorr
 
+from sweep_util import f16_pool_np
 from test_corr_gpu import pyr_np, special_coords
 from test_out_dtype_gpu import assert_same_half
 
@@ -31,16 +32,6 @@ F16 = torch.float16
 # (test_corr_gpu.test_bf16_mma_vs_oracle) scaled by the 2^-3 ratio of the two
 # formats' rounding units.
 F16_TOL = 1e-3
-
-
-def f16_pool_np(level):
-    """One pooling step of an fp16 level (given widened to fp32): the mean in
-    fp32, rounded to fp16 (nearest even), widened again."""
-    lv = np.asarray(level, np.float32)
-    Wo = lv.shape[1] // 2
-    with np.errstate(invalid="ignore", over="ignore"):
-        pm = (lv[:, 0:2 * Wo:2] + lv[:, 1:2 * Wo:2]) * np.float32(0.5)
-        return pm.astype(np.float16).astype(np.float32)
 
 
 # ------------------------------------------------------------ 1. pyramid vs oracle

@@ -72,7 +72,8 @@ from golden_util import norm_err, rel_l2, same
 from oracle import coracle
 from raft_stereo_amd import _lib
 from raft_stereo_amd import corr as rcorr
-from test_corr_gpu import bf16_pool_np, special_coords
+from sweep_util import bf16_pool_np, integer_sweep
+from test_corr_gpu import special_coords
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -236,11 +237,6 @@ def record_padding_zero(rec, W2):
     outside = np.where(s < 26, (e2 < 0) | (e2 >= W2 >> 2), (e0 < 0) | (e0 >= W2))
     bits = rec.contiguous().view(torch.int16).cpu().numpy()
     return not (bits[:, outside] & 0x7FFF).any()
-
-
-def integer_sweep(W2):
-    k = np.arange(-40, W2 + 41, dtype=np.float32)
-    return np.concatenate([k, np.nextafter(k, np.float32(np.inf)), np.nextafter(k, np.float32(-np.inf))])
 
 
 @pytest.mark.parametrize("band", su.REC_W2_BANDS, ids=band_id)
