@@ -484,6 +484,42 @@ int rc_convex_upsample_backward(const float *flow, const float *mask, const floa
                                 int N, int C, int H, int W, int factor,
                                 float *grad_flow, float *grad_mask, float *workspace, void *stream);
 
+/* The elementwise glue of the ConvGRU update between its convolutions (added
+ * within ABI v13), two memory-bound launches:
+ *   rc_gru_gates:  z_out  = sigmoid(z_pre + cz)
+ *                  rh_out = sigmoid(r_pre + cr) * h
+ *   rc_gru_blend:  h_out  = (1 - z) * h + z * tanh(q_pre + cq)
+ *   Operands: N x C x HW arrays of one element type `dtype` (RC_F32, RC_F16 or
+ *   RC_BF16), operand k addressed by strides[3k .. 3k+2] = its (batch,
+ *   channel, pixel) strides in elements, in the order of the pointer
+ *   arguments (7 triples for gates, 5 for blend).  One call therefore takes
+ *   dense NCHW tensors, channel slices of a larger buffer (the two halves of
+ *   a stacked z/r convolution output; the first C channels of the [r*h, x]
+ *   convolution input, whose other channels are not touched) and
+ *   channels-last tensors.  All operands of a call are of one layout class:
+ *   planar (every pixel stride 1) or interleaved (every channel stride 1); a
+ *   stride along an axis of length 1 is ignored.  Any other mix is
+ *   RC_EUNSUPPORTED, whatever N is.  Accesses are 16 bytes per lane where
+ *   every base address and stride and the unit-stride length allow, else 8,
+ *   else one element; all paths give the same bits.
+ *   Arithmetic: fp32 on the widened inputs, every operation of the
+ *   expressions above rounded on its own, one rounding to nearest even at
+ *   the store: an fp16 / bf16 result is Tensor.to(dtype) of the fp32 result on
+ *   the widened inputs, bit for bit.  sigmoid is 0 / 1 and tanh -1 / +1
+ *   exactly at +-inf and wherever they saturate (never NaN); NaN in, NaN out.
+ *   Aliasing: z_out may be z_pre and h_out may be h (exactly, same strides);
+ *   rh_out must not be h (RC_EINVAL); no other overlap between an output and
+ *   an operand.
+ *   RC_EINVAL: an unknown dtype, C < 1, N < 0, HW < 0, a null stride array, a
+ *   negative stride and, with N*HW > 0, a null operand or one not aligned to
+ *   its element size.  N*HW == 0: RC_OK, nothing launched.  N*C*HW >= 2^32:
+ *   RC_EUNSUPPORTED.  All checks run before the launch. */
+int rc_gru_gates(const void *z_pre, const void *r_pre, const void *cz, const void *cr, const void *h,
+                 void *z_out, void *rh_out, const long *strides, int dtype, int N, int C, long HW,
+                 void *stream);
+int rc_gru_blend(const void *z, const void *q_pre, const void *cq, const void *h, void *h_out,
+                 const long *strides, int dtype, int N, int C, long HW, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

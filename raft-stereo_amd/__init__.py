@@ -6,6 +6,9 @@ The package holds only the hot path named by BASELINE.json's north_star:
   * ``corr``    the drop-in ``CorrBlock1D`` mirroring /root/reference/model.py:283-326
                 (constructor, ``__call__(coords)``, ``corr`` staticmethod,
                 ``corr_pyramid`` attribute) plus ``coords_grid`` (:329-332);
+  * ``gru``     the ConvGRU update with its elementwise glue on two kernels
+                (``RAFTStereo(fuse_gru=True)``; the convolutions stay on
+                PyTorch);
   * ``_lib``    the ctypes binding of libraftcorr.so.  There is no CPU
                 fallback: without the built library or a HIP device the
                 calls raise.

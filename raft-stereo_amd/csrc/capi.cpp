@@ -905,3 +905,71 @@ extern "C" int rc_convex_upsample_backward(const float *flow, const float *mask,
                                                 reinterpret_cast<hipStream_t>(stream)),
                   "rc_convex_upsample_backward: launch");
 }
+
+namespace {
+// The checks of rc_gru_gates / rc_gru_blend on their nops operands (the last
+// nout of them outputs); fills `a`.  *empty: nothing to do (RC_OK).
+int prep_gru(const char *who, void *const *ops, const char *const *names, int nops, const long *strides,
+             int dtype, int N, int C, long HW, rc::GruArgs &a, bool *empty) {
+    if (dtype != RC_F32 && dtype != RC_F16 && dtype != RC_BF16)
+        return fail(RC_EINVAL, "%s: unknown dtype %d (RC_F32, RC_F16 or RC_BF16)", who, dtype);
+    if (N < 0 || C < 1 || HW < 0) return fail(RC_EINVAL, "%s: bad shape N=%d C=%d HW=%ld", who, N, C, HW);
+    if (!strides) return fail(RC_EINVAL, "%s: null stride array", who);
+    bool planar = true, inter = true;
+    for (int k = 0; k < nops; ++k) {
+        const long *t = strides + 3 * k;
+        if (t[0] < 0 || t[1] < 0 || t[2] < 0)
+            return fail(RC_EINVAL, "%s: negative stride of %s (%ld, %ld, %ld)", who, names[k], t[0], t[1], t[2]);
+        planar = planar && (HW <= 1 || t[2] == 1);
+        inter = inter && (C == 1 || t[1] == 1);
+    }
+    if (!planar && !inter)
+        return fail(RC_EUNSUPPORTED, "%s: the operands share no layout class: every pixel stride 1 (planar) "
+                    "or every channel stride 1 (interleaved)", who);
+    *empty = (long long)N * HW == 0;
+    if (*empty) return RC_OK;
+    if (HW > 0x7FFFFFFFL || (long long)N * C * HW > 0xFFFFFFFFLL)
+        return fail(RC_EUNSUPPORTED, "%s: N*C*HW = %lld elements exceed 2^32 - 1", who, (long long)N * C * HW);
+    const uintptr_t esize = dtype == RC_F32 ? 4 : 2;
+    a.N = N;
+    a.O = (uint32_t)(planar ? C : HW);
+    a.L = planar ? HW : C;
+    for (int k = 0; k < nops; ++k) {
+        if (!ops[k]) return fail(RC_EINVAL, "%s: null %s", who, names[k]);
+        if (reinterpret_cast<uintptr_t>(ops[k]) % esize)
+            return fail(RC_EINVAL, "%s: %s is not aligned to its element size", who, names[k]);
+        a.op[k] = rc::GruOperand{ops[k], strides[3 * k], strides[3 * k + (planar ? 1 : 2)]};
+    }
+    return RC_OK;
+}
+}  // namespace
+
+extern "C" int rc_gru_gates(const void *z_pre, const void *r_pre, const void *cz, const void *cr,
+                            const void *h, void *z_out, void *rh_out, const long *strides, int dtype, int N,
+                            int C, long HW, void *stream) {
+    g_err[0] = 0;
+    const char *who = "rc_gru_gates";
+    void *const ops[7] = {const_cast<void *>(z_pre), const_cast<void *>(r_pre), const_cast<void *>(cz),
+                          const_cast<void *>(cr), const_cast<void *>(h), z_out, rh_out};
+    const char *const names[7] = {"z_pre", "r_pre", "cz", "cr", "h", "z_out", "rh_out"};
+    rc::GruArgs a;
+    bool empty;
+    if (int rc = prep_gru(who, ops, names, 7, strides, dtype, N, C, HW, a, &empty)) return rc;
+    if (empty) return RC_OK;
+    if (rh_out == h) return fail(RC_EINVAL, "%s: rh_out must not alias h (the blend reads h)", who);
+    return hip_rc(rc_launch_gru(a, dtype, false, reinterpret_cast<hipStream_t>(stream)), "rc_gru_gates: launch");
+}
+
+extern "C" int rc_gru_blend(const void *z, const void *q_pre, const void *cq, const void *h, void *h_out,
+                            const long *strides, int dtype, int N, int C, long HW, void *stream) {
+    g_err[0] = 0;
+    const char *who = "rc_gru_blend";
+    void *const ops[5] = {const_cast<void *>(z), const_cast<void *>(q_pre), const_cast<void *>(cq),
+                          const_cast<void *>(h), h_out};
+    const char *const names[5] = {"z", "q_pre", "cq", "h", "h_out"};
+    rc::GruArgs a;
+    bool empty;
+    if (int rc = prep_gru(who, ops, names, 5, strides, dtype, N, C, HW, a, &empty)) return rc;
+    if (empty) return RC_OK;
+    return hip_rc(rc_launch_gru(a, dtype, true, reinterpret_cast<hipStream_t>(stream)), "rc_gru_blend: launch");
+}

@@ -253,6 +253,22 @@ struct BuildBwdArgs {
     int dev_only;                   // dev library timing probe: 1 = dF1 tiles only, 2 = dF2 only
 };
 
+// rc_gru_gates / rc_gru_blend (gru_gates.hip).  An operand is N images of O
+// rows of L unit-stride elements: the rows are channels and the elements
+// pixels for the planar layout class, pixels and channels for the interleaved
+// one.  Strides in elements.
+struct GruOperand {
+    void *p;
+    long long sn, so;         // batch stride, row stride
+};
+struct GruArgs {
+    GruOperand op[7];         // gates: z_pre r_pre cz cr h z_out rh_out; blend: z q_pre cq h h_out
+    int N;
+    uint32_t O;
+    long long L;
+    uint32_t J, units;        // set by the launcher: work units per row, and in all (< 2^32)
+};
+
 // CUs of the device current at the first call, taken once: every GPU of a
 // node this project runs on is the same.  256 when the query fails.
 inline int device_cus() {
@@ -308,6 +324,8 @@ hipError_t rc_launch_lookup_bwd_calls(rc::LookupBwdCallsArgs &a, int radius, int
 bool rc_lookup_bwd_calls_fits(const rc::LookupBwdCallsArgs &a, int radius, int levels, const long *cbs,
                               int n_calls);
 hipError_t rc_launch_volume_bwd(const rc::BuildBwdArgs &a, hipStream_t s);
+// the ConvGRU gate / blend kernel on operands of element kind ek (gru_gates.hip)
+hipError_t rc_launch_gru(const rc::GruArgs &a, int ek, bool blend, hipStream_t s);
 hipError_t rc_launch_convex_upsample(const float *flow, const float *mask, int N, int C, int H,
                                      int W, int factor, float *out, hipStream_t s);
 // grad_flow / grad_mask may be null (not computed); workspace is read only with grad_flow

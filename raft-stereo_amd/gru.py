@@ -1,0 +1,260 @@
+"""The ConvGRU update with its elementwise glue on two gfx950 kernels
+(rc_gru_gates, rc_gru_blend; csrc/gru_gates.hip).
+
+``ConvGRU.forward`` (network.py) is three convolutions surrounded by two
+concatenations and about eleven elementwise launches.  ``conv_gru_forward``
+keeps the convolutions where they are and runs the rest as
+
+  1. one ``torch.cat`` of h and every part of x into the [h, x] buffer,
+  2. convz and convr as one stacked convolution (``_zr_conv``),
+  3. ``gru_gates``: z in place on the convolution output, r*h over the first
+     C channels of the [h, x] buffer, which thereby becomes [r*h, x],
+  4. convq on that buffer,
+  5. ``gru_blend``: the new hidden state.
+
+It is opt-in (``ConvGRU.fuse``, ``RAFTStereo(fuse_gru=True)``), inference-only
+-- with a gradient being recorded ``fusable`` is false and the PyTorch ops run
+-- and has no CPU fallback: the wrappers raise on tensors that are not on a
+HIP device.
+"""
+import weakref
+
+import torch
+import torch.nn.functional as F
+
+from . import _lib
+
+_CODES = {torch.float32: _lib.RC_F32, torch.float16: _lib.RC_F16, torch.bfloat16: _lib.RC_BF16}
+
+_ZR = weakref.WeakKeyDictionary()   # ConvGRU -> (weight, bias, C, tag): convz and convr stacked
+_ZR_CAST = weakref.WeakKeyDictionary()   # ConvGRU -> (stacked weight, dtype, weight cast, bias cast)
+
+
+def _zr_conv(gru):
+    """convz and convr as ONE conv (weights stacked along the output channels):
+    the same per-channel sums, one launch instead of two and no sliced input
+    for convz -- at 60-row slabs each launch's fixed cost matters (DESIGN.md
+    §5).  Cached per module only while no gradient is recorded (a cached
+    autograd node could not be back-propagated twice); the cache entry is
+    keyed on each weight's storage, in-place version, dtype and device, so
+    ``.to()`` / ``.double()`` / ``load_state_dict`` (which keep the Parameter
+    object) rebuild it."""
+    wz, wr = gru.convz.weight, gru.convr.weight
+    bz, br = gru.convz.bias, gru.convr.bias
+    ws = [t for t in (wz, wr, bz, br) if t is not None]
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ws):
+        w = torch.cat([wz, wr], 0)
+        return w, (None if bz is None else torch.cat([bz, br], 0)), wz.shape[0]
+    tag = tuple((t.data_ptr(), t._version, t.dtype, t.device) for t in ws)
+    hit = _ZR.get(gru)
+    if hit is None or hit[3] != tag:
+        w = torch.cat([wz, wr], 0)
+        b = None if bz is None else torch.cat([bz, br], 0)
+        hit = _ZR[gru] = (w, b, wz.shape[0], tag)
+    return hit[0], hit[1], hit[2]
+
+
+def _zr_conv_as(gru, dtype):
+    """``_zr_conv`` in ``dtype`` (no gradient recorded): under autocast the
+    stacked weights are no leaf, so autocast's own cast cache would convert
+    them at every call; the cast is kept with the entry it was made from."""
+    w, b, C = _zr_conv(gru)
+    if w.dtype == dtype:
+        return w, b, C
+    hit = _ZR_CAST.get(gru)
+    if hit is None or hit[0] is not w or hit[1] != dtype:
+        hit = _ZR_CAST[gru] = (w, dtype, w.to(dtype), None if b is None else b.to(dtype))
+    return hit[2], hit[3], C
+
+
+def _triple(t):
+    """(batch, channel, pixel) strides in elements of a 4-D tensor whose H and
+    W merge into one pixel axis, else None."""
+    _, _, H, W = t.shape
+    sn, sc, sh, sw = t.stride()
+    if H == 1:
+        return sn, sc, (1 if W == 1 else sw)
+    if W == 1:
+        return sn, sc, sh
+    return (sn, sc, sw) if sh == W * sw else None
+
+
+def _classes(t):
+    """The layout classes a tensor fits: subset of {'planar', 'interleaved'}."""
+    tr = _triple(t)
+    if tr is None:
+        return set()
+    _, C, H, W = t.shape
+    out = set()
+    if H * W <= 1 or tr[2] == 1:
+        out.add("planar")
+    if C == 1 or tr[1] == 1:
+        out.add("interleaved")
+    return out
+
+
+def _common_class(tensors):
+    cls = {"planar", "interleaved"}
+    for t in tensors:
+        cls &= _classes(t)
+    return cls
+
+
+def _compute_dtype(gru, h):
+    """The dtype the gate convolutions compute and return in: autocast's on a
+    HIP tensor inside an autocast region, else the weights'."""
+    if h.device.type == "cuda" and torch.is_autocast_enabled():
+        return torch.get_autocast_dtype("cuda")
+    return gru.convz.weight.dtype
+
+
+def why_not_fusable(gru, h, cz, cr, cq, *x_list):
+    """None when ``conv_gru_forward`` can stand in for ``ConvGRU.forward`` on
+    these arguments, else the first reason why not, in words."""
+    state = (h, cz, cr, cq)
+    tensors = state + tuple(x_list)
+    if not x_list or any(not isinstance(t, torch.Tensor) or t.dim() != 4 for t in tensors):
+        return "h, cz, cr, cq and at least one part of x, all 4-D tensors"
+    dt = h.dtype
+    if dt not in _CODES:
+        return f"dtype {dt}: float32, float16 or bfloat16"
+    if any(t.dtype != dt for t in state):
+        return "h, cz, cr and cq of mixed dtypes"
+    autocast = h.device.type == "cuda" and torch.is_autocast_enabled()
+    if dt != _compute_dtype(gru, h):
+        return f"h is {dt}, the gate convolutions compute in {_compute_dtype(gru, h)}"
+    # under autocast the convolution casts its input, so the parts of x may be
+    # of another float dtype (the motion features carry the fp32 flow)
+    if any(t.dtype != dt and not (autocast and t.dtype in _CODES) for t in x_list):
+        return "x parts of mixed dtypes outside autocast"
+    if any(t.shape != h.shape for t in state) or any(t.shape[0] != h.shape[0] or t.shape[2:] != h.shape[2:]
+                                                       for t in x_list):
+        return "shapes do not match h's"
+    cz_, cr_, cq_ = gru.convz, gru.convr, gru.convq
+    if torch.is_grad_enabled():
+        params = [p for c in (cz_, cr_, cq_) for p in (c.weight, c.bias) if p is not None]
+        if any(t.requires_grad for t in tensors) or any(p.requires_grad for p in params):
+            return "a gradient is being recorded (there is no backward kernel)"
+    if h.device.type != "cuda":
+        return f"h is on {h.device}: HIP devices only"
+    if any(t.device != h.device for t in tensors) or cz_.weight.device != h.device:
+        return "tensors on different devices"
+    if not _common_class(state):
+        return "h, cz, cr and cq share no layout class with a mergeable H*W"
+    if any(type(c) is not torch.nn.Conv2d for c in (cz_, cr_, cq_)):
+        return "gates that are not nn.Conv2d"
+    geom = [(c.kernel_size, c.stride, c.padding, c.dilation, c.groups, c.padding_mode, c.bias is None)
+            for c in (cz_, cr_)]
+    if geom[0] != geom[1] or cz_.stride != (1, 1) or cz_.groups != 1 or cz_.padding_mode != "zeros":
+        return "convz and convr cannot be stacked"
+    if cz_.weight.shape[0] != h.shape[1]:
+        return "convz does not return h's channels"
+    return None
+
+
+def fusable(gru, h, cz, cr, cq, *x_list):
+    """Whether ``conv_gru_forward`` can stand in for ``ConvGRU.forward`` on
+    these arguments: every tensor on one HIP device; h, cz, cr and cq of one
+    dtype out of fp32 / fp16 / bf16, the one the gate convolutions compute in
+    (the parts of x may be of other float dtypes only under autocast, where
+    the convolution would cast them anyway); h, cz, cr and cq of one layout
+    class with a mergeable H*W; convz and convr of one geometry; and no
+    gradient being recorded for any input or gate weight."""
+    return why_not_fusable(gru, h, cz, cr, cq, *x_list) is None
+
+
+def _check(name, ops, names):
+    first = ops[0]
+    for t, n in zip(ops, names):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: {n} must be a torch.Tensor")
+        if t.device.type != "cuda":
+            raise RuntimeError(f"{name}: {n} is on {t.device}; the kernel runs on HIP devices only "
+                               "(no CPU fallback)")
+        if t.device != first.device:
+            raise RuntimeError(f"{name}: {n} is on {t.device}, {names[0]} on {first.device}")
+        if t.dtype != first.dtype:
+            raise ValueError(f"{name}: {n} is {t.dtype}, {names[0]} is {first.dtype}: one dtype for all operands")
+        if t.dim() != 4 or t.shape != first.shape:
+            raise ValueError(f"{name}: {n} has shape {tuple(t.shape)}, {names[0]} has {tuple(first.shape)}")
+    if first.dtype not in _CODES:
+        raise ValueError(f"{name}: dtype {first.dtype}: float32, float16 or bfloat16")
+    triples = []
+    for t, n in zip(ops, names):
+        tr = _triple(t)
+        if tr is None:
+            raise ValueError(f"{name}: H and W of {n} do not merge into one pixel axis (strides {t.stride()})")
+        triples += tr
+    return _lib.long_array(triples)
+
+
+def _empty_like_class(ref, cls):
+    fmt = torch.channels_last if "planar" not in cls else torch.contiguous_format
+    return torch.empty(ref.shape, dtype=ref.dtype, device=ref.device, memory_format=fmt)
+
+
+def gru_gates(z_pre, r_pre, cz, cr, h, z_out=None, rh_out=None):
+    """z = sigmoid(z_pre + cz) and r*h with r = sigmoid(r_pre + cr), one launch
+    (rc_gru_gates).  All operands (N, C, H, W) of one dtype and one layout
+    class; any of them may be a channel slice of a larger tensor.  ``z_out``
+    may be ``z_pre``; ``rh_out`` must not be ``h``.  Missing outputs are
+    allocated.  Returns (z_out, rh_out)."""
+    cls = _common_class((z_pre, r_pre, cz, cr, h))
+    if z_out is None:
+        z_out = _empty_like_class(h, cls)
+    if rh_out is None:
+        rh_out = _empty_like_class(h, cls)
+    ops = (z_pre, r_pre, cz, cr, h, z_out, rh_out)
+    strides = _check("gru_gates", ops, ("z_pre", "r_pre", "cz", "cr", "h", "z_out", "rh_out"))
+    N, C, H, W = h.shape
+    with torch.cuda.device(h.device):
+        stream = torch.cuda.current_stream(h.device).cuda_stream or None
+        rc = _lib.lib().rc_gru_gates(*(t.data_ptr() for t in ops), strides, _CODES[h.dtype], N, C, H * W, stream)
+    _lib.check(rc, "rc_gru_gates")
+    return z_out, rh_out
+
+
+def gru_blend(z, q_pre, cq, h, h_out=None):
+    """h_out = (1 - z) * h + z * tanh(q_pre + cq), one launch (rc_gru_blend).
+    Operands as for ``gru_gates``; ``h_out`` may be ``h`` and is allocated
+    when missing.  Returns h_out."""
+    if h_out is None:
+        h_out = _empty_like_class(h, _common_class((z, q_pre, cq, h)))
+    ops = (z, q_pre, cq, h, h_out)
+    strides = _check("gru_blend", ops, ("z", "q_pre", "cq", "h", "h_out"))
+    N, C, H, W = h.shape
+    with torch.cuda.device(h.device):
+        stream = torch.cuda.current_stream(h.device).cuda_stream or None
+        rc = _lib.lib().rc_gru_blend(*(t.data_ptr() for t in ops), strides, _CODES[h.dtype], N, C, H * W, stream)
+    _lib.check(rc, "rc_gru_blend")
+    return h_out
+
+
+def _as_class(t, cls):
+    """t itself when it fits a class of ``cls``, else a copy that does (a
+    convolution that answered in another memory format than its input's)."""
+    if _classes(t) & cls:
+        return t
+    return t.contiguous(memory_format=torch.contiguous_format if "planar" in cls else torch.channels_last)
+
+
+def conv_gru_forward(gru, h, cz, cr, cq, *x_list):
+    """``ConvGRU.forward`` for arguments that are ``fusable``: the same three
+    convolutions, one concatenation and two elementwise launches (module
+    docstring).  Returns the new hidden state, a new tensor in h's layout."""
+    cls = _common_class((h, cz, cr, cq))
+    if not cls:
+        raise ValueError("conv_gru_forward: h, cz, cr and cq share no layout class (see gru.fusable)")
+    dt = h.dtype
+    N, C, H, W = h.shape
+    Cx = sum(x.shape[1] for x in x_list)
+    fmt = torch.contiguous_format if "planar" in cls else torch.channels_last
+    hx = torch.empty((N, C + Cx, H, W), dtype=dt, device=h.device, memory_format=fmt)
+    torch.cat([h, *x_list], dim=1, out=hx)
+    one = {"planar"} if "planar" in cls else {"interleaved"}
+    w, b, _ = _zr_conv_as(gru, dt)
+    zr = _as_class(F.conv2d(hx, w, b, padding=gru.convz.padding, dilation=gru.convz.dilation), one)
+    z = zr[:, :C]
+    gru_gates(z, zr[:, C:], cz, cr, h, z_out=z, rh_out=hx[:, :C])      # hx is now [r*h, x]
+    q = _as_class(gru.convq(hx), one)
+    return gru_blend(z, q, cq, h)

@@ -26,6 +26,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import gru as _gru
 from .corr import CorrBlock1D, coords_grid
 
 
@@ -136,7 +137,15 @@ class BasicEncoder(nn.Module):
 
 
 class ConvGRU(nn.Module):
-    """Convolutional GRU with additive context biases cz, cr, cq (model.py:164-179)."""
+    """Convolutional GRU with additive context biases cz, cr, cq (model.py:164-179).
+
+    ``fuse`` (a plain attribute, not in the state_dict; off by default): run
+    the glue between the three convolutions on the two gfx950 kernels of
+    gru.py wherever ``gru.fusable`` holds -- HIP tensors of one dtype and
+    layout class, no gradient being recorded; anything else takes the PyTorch
+    ops below, unchanged."""
+
+    fuse = False
 
     def __init__(self, hidden_dim, input_dim, kernel_size=3):
         super().__init__()
@@ -145,6 +154,8 @@ class ConvGRU(nn.Module):
             setattr(self, gate, nn.Conv2d(hidden_dim + input_dim, hidden_dim, kernel_size, padding=pad))
 
     def forward(self, h, cz, cr, cq, *x_list):
+        if self.fuse and _gru.fusable(self, h, cz, cr, cq, *x_list):
+            return _gru.conv_gru_forward(self, h, cz, cr, cq, *x_list)
         x = torch.cat(x_list, dim=1)
         hx = torch.cat([h, x], dim=1)
         z = torch.sigmoid(self.convz(hx) + cz)
@@ -234,7 +245,7 @@ class RAFTStereo(nn.Module):
     """model.py:335-383 with the correlation block pluggable (``corr_block``)."""
 
     def __init__(self, args, corr_block=None, fuse_convc1=False, fuse_step=False, corr_out_dtype=None,
-                 corr_pyramid_dtype=None):
+                 corr_pyramid_dtype=None, fuse_gru=False):
         super().__init__()
         self.args = args
         # corr_out_dtype (DESIGN.md §3.2j): the lookup output's dtype (with
@@ -274,6 +285,12 @@ class RAFTStereo(nn.Module):
         # the loop's coords update and flow inside the
         # lookup launch (CorrBlock1D.lookup_step); exclusive with fuse_convc1
         self.fuse_step = fuse_step
+        # the three ConvGRUs' elementwise glue on two kernels
+        # (gru.conv_gru_forward); inference only -- while a gradient is being
+        # recorded the PyTorch ops run.  Independent of the corr options above.
+        self.fuse_gru = bool(fuse_gru)
+        for name in ("gru08", "gru16", "gru32"):
+            getattr(self.update_block, name).fuse = self.fuse_gru
 
     def initialize_flow(self, img):
         N, _, H, W = img.shape

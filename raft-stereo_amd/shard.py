@@ -15,13 +15,13 @@ way, exchanging only the GRU state halos each iteration.
 """
 import contextlib
 import time
-import weakref
 
 import torch
 import torch.distributed as dist
 import torch.nn.functional as F
 
 from .corr import CorrBlock1D, coords_grid
+from .gru import _ZR, _zr_conv  # noqa: F401  (the stacked z/r conv and its cache live in gru.py)
 
 
 def _host_staged(t, group=None):
@@ -238,33 +238,6 @@ def _cat_rows(parts, lo, hi):
     image (one copy, as the full op's torch.cat)."""
     s0, s1 = parts[0].clip(lo, hi)
     return _Rows(torch.cat([p.rows(s0, s1) for p in parts], 1), s0, parts[0].H)
-
-
-_ZR = weakref.WeakKeyDictionary()   # ConvGRU -> (weight, bias, C, tag): convz and convr stacked
-
-
-def _zr_conv(gru):
-    """convz and convr as ONE conv (weights stacked along the output channels):
-    the same per-channel sums, one launch instead of two and no sliced input
-    for convz -- at 60-row slabs each launch's fixed cost matters (DESIGN.md
-    §5).  Cached per module only while no gradient is recorded (a cached
-    autograd node could not be back-propagated twice); the cache entry is
-    keyed on each weight's storage, in-place version, dtype and device, so
-    ``.to()`` / ``.double()`` / ``load_state_dict`` (which keep the Parameter
-    object) rebuild it."""
-    wz, wr = gru.convz.weight, gru.convr.weight
-    bz, br = gru.convz.bias, gru.convr.bias
-    ws = [t for t in (wz, wr, bz, br) if t is not None]
-    if torch.is_grad_enabled() and any(t.requires_grad for t in ws):
-        w = torch.cat([wz, wr], 0)
-        return w, (None if bz is None else torch.cat([bz, br], 0)), wz.shape[0]
-    tag = tuple((t.data_ptr(), t._version, t.dtype, t.device) for t in ws)
-    hit = _ZR.get(gru)
-    if hit is None or hit[3] != tag:
-        w = torch.cat([wz, wr], 0)
-        b = None if bz is None else torch.cat([bz, br], 0)
-        hit = _ZR[gru] = (w, b, wz.shape[0], tag)
-    return hit[0], hit[1], hit[2]
 
 
 def _gru_rows(gru, h, cz, cr, cq, xs, lo, hi, fuse_zr=True):

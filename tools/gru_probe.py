@@ -1,0 +1,196 @@
+"""The fused ConvGRU glue (raft-stereo_amd/gru.py) against the
+PyTorch ops it replaces, alternated in one process.
+
+  kernels  rc_gru_gates + rc_gru_blend (and the single concatenation of the
+           fused route) against the torch op sequence of ConvGRU.forward
+           between its convolutions (two concatenations of x, the [r*h, x]
+           concatenation, three adds, two sigmoids, tanh, r*h, 1-z, two
+           multiplies, an add), at the gru08 / gru16 / gru32 sizes of config 2
+           (B = 8, 128 channels, 135x240 / 68x120 / 34x60), fp32 and bf16, NCHW
+           and NHWC.  Device-event times over --reps calls, the two sides
+           alternated --rounds times: median and min..max of the rounds.  The
+           kernels' bytes (7 and 5 operands of N*C*H*W elements) over their
+           time, against the 6.29 TB/s measured copy rate of the MI355X.
+  e2e      RAFTStereo at 540x960, B = 8, 32 iterations with and without
+           fuse_gru (one model, the option toggled, alternated), in one of the
+           settings of e2e_probe.py: fp32, bf16 (autocast), bf16_cl (autocast +
+           channels_last + MIOpen autotuning); host clock around synchronised
+           forwards, per-round times, and the final disparities' difference.
+
+    python tools/gru_probe.py kernels [--out profiles/gru_gates.json]
+    python tools/gru_probe.py e2e --setting bf16 [--rounds 3]
+
+Each part merges its results into the --out file under its own key.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import pkgload  # noqa: E402
+
+pkgload.load()
+from raft_stereo_amd import gru  # noqa: E402
+from raft_stereo_amd.network import RAFTStereo, StereoArgs  # noqa: E402
+
+COPY_RATE = 6.29e12      # bytes/s, measured copy rate (MI355X_MICROARCH.md)
+SIZES = {"gru08": (135, 240, (128, 128)), "gru16": (68, 120, (128, 128)), "gru32": (34, 60, (128,))}
+
+
+def device_ms(fn, reps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def alternate(fns, reps, rounds):
+    """{name: [ms per call, one per round]} with the callables taking turns."""
+    for fn in fns.values():
+        fn()
+    torch.cuda.synchronize()
+    out = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            out[k].append(device_ms(fn, reps))
+    return out
+
+
+def summary(ms):
+    return {"median_us": statistics.median(ms) * 1e3, "min_us": min(ms) * 1e3, "max_us": max(ms) * 1e3}
+
+
+def kernels_part(reps, rounds):
+    rows = []
+    N, C = 8, 128
+    for name, (H, W, parts) in SIZES.items():
+        for dt in (torch.float32, torch.bfloat16):
+            for cl in (False, True):
+                g = torch.Generator(device="cuda").manual_seed(0)
+                fmt = torch.channels_last if cl else torch.contiguous_format
+
+                def rnd(ch):
+                    t = torch.randn(N, ch, H, W, device="cuda", generator=g).to(dt)
+                    return t.contiguous(memory_format=fmt)
+
+                h, zr, ctx, qp = torch.tanh(rnd(C)), rnd(2 * C), rnd(3 * C), rnd(C)
+                cz, cr, cq = ctx.split(C, dim=1)
+                xs = [rnd(c) for c in parts]
+                hx = torch.empty((N, C + sum(parts), H, W), dtype=dt, device="cuda", memory_format=fmt)
+                zbuf = torch.empty_like(h)
+                hout = torch.empty_like(h)
+
+                def torch_glue():
+                    x = torch.cat(xs, dim=1)
+                    torch.cat([h, x], dim=1)
+                    z = torch.sigmoid(zr[:, :C] + cz)
+                    r = torch.sigmoid(zr[:, C:] + cr)
+                    torch.cat([r * h, x], dim=1)
+                    q = torch.tanh(qp + cq)
+                    return (1 - z) * h + z * q
+
+                def fused_glue():
+                    torch.cat([h, *xs], dim=1, out=hx)
+                    gru.gru_gates(zr[:, :C], zr[:, C:], cz, cr, h, z_out=zbuf, rh_out=hx[:, :C])
+                    return gru.gru_blend(zbuf, qp, cq, h, h_out=hout)
+
+                fns = {"torch_glue": torch_glue, "fused_glue": fused_glue,
+                       "gates": lambda: gru.gru_gates(zr[:, :C], zr[:, C:], cz, cr, h, z_out=zbuf,
+                                                      rh_out=hx[:, :C]),
+                       "blend": lambda: gru.gru_blend(zbuf, qp, cq, h, h_out=hout)}
+                with torch.no_grad():
+                    ms = alternate(fns, reps, rounds)
+                row = {"size": name, "shape": [N, C, H, W], "x_channels": list(parts),
+                       "dtype": str(dt).replace("torch.", ""), "layout": "NHWC" if cl else "NCHW"}
+                for k, v in ms.items():
+                    row[k] = summary(v)
+                elems = N * C * H * W * h.element_size()
+                for k, nops in (("gates", 7), ("blend", 5)):
+                    rate = nops * elems / (row[k]["median_us"] * 1e-6)
+                    row[k]["bytes"] = nops * elems
+                    row[k]["TB_per_s"] = rate / 1e12
+                    row[k]["of_copy_rate"] = rate / COPY_RATE
+                row["speedup"] = row["torch_glue"]["median_us"] / row["fused_glue"]["median_us"]
+                print(json.dumps(row), flush=True)
+                rows.append(row)
+    return {"reps": reps, "rounds": rounds, "copy_rate_TB_per_s": COPY_RATE / 1e12, "rows": rows}
+
+
+def e2e_part(setting, rounds, B=8, H=540, W=960, iters=32):
+    mixed, bench, cl = {"fp32": (False, False, False), "bf16": (True, False, False),
+                        "bf16_cl": (True, True, True)}[setting]
+    torch.backends.cudnn.benchmark = bench
+    torch.manual_seed(0)
+    args = StereoArgs(mixed_precision=mixed)
+    args.autocast_dtype = torch.bfloat16
+    model = RAFTStereo(args, fuse_gru=True).eval().cuda()
+    if cl:
+        model = model.to(memory_format=torch.channels_last)
+    grus = [getattr(model.update_block, n) for n in ("gru08", "gru16", "gru32")]
+    g = torch.Generator().manual_seed(1234)
+    img1 = (torch.rand(B, 3, H, W, generator=g) * 255).cuda()
+    img2 = torch.roll(img1, -8, dims=-1)
+
+    def forward(fuse):
+        for m in grus:
+            m.fuse = fuse
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = model(img1, img2, iters=iters)[-1]
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    ms = {False: [], True: []}
+    with torch.no_grad():
+        last = {fuse: forward(fuse)[1] for fuse in (False, True)}       # warm-up: every shape of both routes
+        for _ in range(rounds):
+            for fuse in (False, True):
+                t, last[fuse] = forward(fuse)
+                ms[fuse].append(t)
+    diff = (last[True].float() - last[False].float())[:, 0].abs()
+    res = {"setting": setting, "mixed_bf16": mixed, "miopen_benchmark": bench, "channels_last": cl,
+           "shape": [B, H, W], "iters": iters, "rounds": rounds,
+           "unfused_ms": ms[False], "fused_ms": ms[True],
+           "unfused_median_ms": statistics.median(ms[False]), "fused_median_ms": statistics.median(ms[True]),
+           "final_disparity_mae_px": diff.mean().item(), "final_disparity_max_px": diff.max().item()}
+    res["fused_over_unfused"] = res["fused_median_ms"] / res["unfused_median_ms"]
+    print(json.dumps(res), flush=True)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("part", choices=["kernels", "e2e"])
+    ap.add_argument("--setting", choices=["fp32", "bf16", "bf16_cl"], default="bf16")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=None)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gru_gates.json"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("gru_probe: needs a HIP device (no CPU timing)")
+    if a.part == "kernels":
+        key, res = "kernels", kernels_part(a.reps, a.rounds or 7)
+    else:
+        key, res = f"e2e_{a.setting}", e2e_part(a.setting, a.rounds or 3)
+    doc = {}
+    if os.path.exists(a.out):
+        with open(a.out) as fh:
+            doc = json.load(fh)
+    doc[key] = res
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        json.dump(doc, fh, indent=1)
+        fh.write("\n")
+
+
+if __name__ == "__main__":
+    main()
