@@ -458,8 +458,11 @@ int rc_corr_build_backward(const void *fmap1, const void *fmap2, int fmap_dtype,
  *                                 * f * flow[n][c][h + dy_k][w + dx_k]
  *   k = 3 (dy+1) + (dx+1), zeros outside the image (RAFT-Stereo's upsampler,
  *   F.unfold + softmax; the reference builds the mask but never applies it).
- *   flow (N,C,H,W), mask (N,9f^2,H,W), out (N,C,fH,fW): fp32 contiguous.
- *   factor 1, 2, 4 or 8. */
+ *   flow (N,C,H,W), mask (N,9f^2,H,W), out (N,C,fH,fW): fp32 contiguous;
+ *   out aligned to min(16, 4 f) bytes (else RC_EINVAL).  factor 1, 2, 4 or 8.
+ *   Non-finite masks follow the softmax: a -inf tap has weight 0 while another
+ *   tap of its sub-pixel is finite; a sub-pixel whose nine taps are all -inf,
+ *   or that holds +inf or NaN, gives NaN in its output element. */
 int rc_convex_upsample(const float *flow, const float *mask, int N, int C, int H, int W,
                        int factor, float *out, void *stream);
 

@@ -876,6 +876,9 @@ extern "C" int rc_convex_upsample(const float *flow, const float *mask, int N, i
         return fail(RC_EUNSUPPORTED, "rc_convex_upsample: factor %d (1, 2, 4 or 8)", factor);
     if ((long long)N * H * W == 0) return RC_OK;
     if (!flow || !mask || !out) return fail(RC_EINVAL, "rc_convex_upsample: null pointer");
+    // the kernel stores the f outputs of a sub-row as one vector
+    if (reinterpret_cast<uintptr_t>(out) & (uintptr_t)(4 * std::min(factor, 4) - 1))
+        return fail(RC_EINVAL, "rc_convex_upsample: out must be %d-byte aligned", 4 * std::min(factor, 4));
     return hip_rc(rc_launch_convex_upsample(flow, mask, N, C, H, W, factor, out,
                                             reinterpret_cast<hipStream_t>(stream)),
                   "rc_convex_upsample: launch");

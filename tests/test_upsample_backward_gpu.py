@@ -100,6 +100,36 @@ def test_expanded_grad_out():
     assert torch.equal(s_flow, o_flow) and torch.equal(s_mask, o_mask)
 
 
+@pytest.mark.parametrize("f", [2, 4])
+def test_unaligned_grad_out(f):
+    """A contiguous grad_out one float into its storage: 4 mod 16 bytes, which
+    rc_convex_upsample_backward refuses at f >= 2 (its vector load); the
+    wrapper hands the kernel an aligned copy."""
+    shape = (2, 2, 7, 9, f)
+    flow, mask, gout = inputs(shape)
+    store = torch.empty(gout.numel() + 5, device="cuda")
+    lead = (4 - store.data_ptr() % 16) % 16 // 4                   # floats to an address 4 mod 16
+    g = store[lead:lead + gout.numel()].view(gout.shape)
+    g.copy_(gout)
+    assert g.is_contiguous() and g.data_ptr() % 16 == 4
+    from raft_stereo_amd.upsample import convex_upsample
+    fl = flow.cuda().requires_grad_(True)
+    mk = mask.cuda().requires_grad_(True)
+    convex_upsample(fl, mk, f, differentiable=True).backward(g)
+    a_flow, a_mask = hip_grads(flow, mask, gout, f)
+    assert torch.equal(fl.grad, a_flow) and torch.equal(mk.grad, a_mask)
+
+
+def test_empty_batch():
+    from raft_stereo_amd.upsample import convex_upsample
+    fl = torch.empty(0, 2, 7, 9, device="cuda").requires_grad_(True)
+    mk = torch.empty(0, 9 * 16, 7, 9, device="cuda").requires_grad_(True)
+    out = convex_upsample(fl, mk, 4, differentiable=True)
+    assert out.shape == (0, 2, 28, 36) and out.grad_fn is not None
+    out.sum().backward()
+    assert fl.grad.shape == fl.shape and mk.grad.shape == mk.shape
+
+
 def test_bf16_mask_gets_bf16_gradient():
     shape = (2, 2, 7, 9, 4)
     flow, mask, gout = inputs(shape)
