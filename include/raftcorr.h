@@ -55,7 +55,8 @@ extern "C" {
  * The element type RC_F16 was added the same way: a new value of an existing
  * argument that a version-13 caller never passes (a library from before it
  * answers RC_EINVAL "unknown dtype"), no entry point, flag or layout changed,
- * so the number did not move for it either. */
+ * so the number did not move for it either.  rc_gru_gates / rc_gru_blend and
+ * their backward entry points are additive in the same way. */
 #define RC_ABI_VERSION 13
 
 /* element types */
@@ -522,6 +523,38 @@ int rc_gru_gates(const void *z_pre, const void *r_pre, const void *cz, const voi
                  void *stream);
 int rc_gru_blend(const void *z, const void *q_pre, const void *cq, const void *h, void *h_out,
                  const long *strides, int dtype, int N, int C, long HW, void *stream);
+
+/* Backward of rc_gru_gates / rc_gru_blend (added within ABI v13, additive like
+ * the two above: a caller that needs them checks for the symbols), for
+ * training with the fused update block; one launch each.  With the incoming
+ * gradients g_out (of h_out), g_z (of z_out) and g_rh (of rh_out):
+ *   rc_gru_blend_backward:  q      = tanh(q_pre + cq)
+ *                           g_z    = g_out * (q - h)
+ *                           g_qpre = (g_out * z) * (1 - q*q)     also cq's gradient
+ *                           g_h    = g_out * (1 - z)
+ *   rc_gru_gates_backward:  r      = sigmoid(r_pre + cr)
+ *                           g_zpre = g_z * ((1 - z) * z)         also cz's gradient
+ *                           g_rpre = (g_rh * h) * ((1 - r) * r)  also cr's gradient
+ *                           g_h    = g_rh * r
+ *   z is the forward's output; r and q are recomputed from the pre-activations
+ *   exactly as the forward computes them, so nothing else is kept.  Each g_h
+ *   is that kernel's contribution to h's gradient; the caller adds them.
+ *   Operands, strides (9 triples for gates, 8 for blend, in pointer order),
+ *   layout classes, access widths, arithmetic (fp32 on the widened inputs,
+ *   every operation above rounded on its own, one rounding at the store) and
+ *   the RC_EINVAL / RC_EUNSUPPORTED / RC_OK cases are rc_gru_gates'.  Where
+ *   the forward saturates (sigmoid 0 / 1, tanh +-1) g_zpre, g_rpre and g_qpre
+ *   are +-0 for finite incoming gradients; NaN in, NaN out.
+ *   Aliasing: an output may be an input (exactly, same strides: g_zpre over
+ *   g_z, g_h over g_out); two outputs in one array are RC_EINVAL.  g_zpre and
+ *   g_rpre are normally the channel halves of one (N, 2C) buffer, the
+ *   gradient of the stacked z/r convolution's output. */
+int rc_gru_gates_backward(const void *g_z, const void *g_rh, const void *z, const void *r_pre, const void *cr,
+                          const void *h, void *g_zpre, void *g_rpre, void *g_h,
+                          const long *strides, int dtype, int N, int C, long HW, void *stream);
+int rc_gru_blend_backward(const void *g_out, const void *z, const void *q_pre, const void *cq, const void *h,
+                          void *g_z, void *g_qpre, void *g_h,
+                          const long *strides, int dtype, int N, int C, long HW, void *stream);
 
 #ifdef __cplusplus
 }

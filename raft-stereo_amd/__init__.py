@@ -8,7 +8,8 @@ The package holds only the hot path named by BASELINE.json's north_star:
                 ``corr_pyramid`` attribute) plus ``coords_grid`` (:329-332);
   * ``gru``     the ConvGRU update with its elementwise glue on two kernels
                 (``RAFTStereo(fuse_gru=True)``; the convolutions stay on
-                PyTorch);
+                PyTorch) and, for training, its backward on two more
+                (``fuse_gru_backward=True``);
   * ``_lib``    the ctypes binding of libraftcorr.so.  There is no CPU
                 fallback: without the built library or a HIP device the
                 calls raise.

@@ -88,6 +88,8 @@ SIGNATURES = {
                                     ctypes.POINTER(_l), _i, _vp, _vp, _vp]),
     "rc_gru_gates": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_l), _i, _i, _i, _l, _vp]),
     "rc_gru_blend": (_i, [_vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_l), _i, _i, _i, _l, _vp]),
+    "rc_gru_gates_backward": (_i, [_vp] * 9 + [ctypes.POINTER(_l), _i, _i, _i, _l, _vp]),
+    "rc_gru_blend_backward": (_i, [_vp] * 8 + [ctypes.POINTER(_l), _i, _i, _i, _l, _vp]),
 }
 
 _lib = None

@@ -910,10 +910,12 @@ extern "C" int rc_convex_upsample_backward(const float *flow, const float *mask,
 }
 
 namespace {
-// The checks of rc_gru_gates / rc_gru_blend on their nops operands (the last
-// nout of them outputs); fills `a`.  *empty: nothing to do (RC_OK).
+// The checks of rc_gru_gates / rc_gru_blend and their backward entry points on
+// their nops operands; fills `a` (rc::GruArgs or rc::GruBwdArgs).  *empty:
+// nothing to do (RC_OK).
+template <class Args>
 int prep_gru(const char *who, void *const *ops, const char *const *names, int nops, const long *strides,
-             int dtype, int N, int C, long HW, rc::GruArgs &a, bool *empty) {
+             int dtype, int N, int C, long HW, Args &a, bool *empty) {
     if (dtype != RC_F32 && dtype != RC_F16 && dtype != RC_BF16)
         return fail(RC_EINVAL, "%s: unknown dtype %d (RC_F32, RC_F16 or RC_BF16)", who, dtype);
     if (N < 0 || C < 1 || HW < 0) return fail(RC_EINVAL, "%s: bad shape N=%d C=%d HW=%ld", who, N, C, HW);
@@ -945,6 +947,24 @@ int prep_gru(const char *who, void *const *ops, const char *const *names, int no
     }
     return RC_OK;
 }
+
+// The backward entry points: prep_gru, then the outputs (the last nout
+// operands) must be nout different arrays, then the launch.
+int gru_backward(const char *who, void *const *ops, const char *const *names, int nops, int nout,
+                 const long *strides, int dtype, int N, int C, long HW, bool blend, void *stream) {
+    g_err[0] = 0;
+    rc::GruBwdArgs a;
+    bool empty;
+    if (int rc = prep_gru(who, ops, names, nops, strides, dtype, N, C, HW, a, &empty)) return rc;
+    if (empty) return RC_OK;
+    for (int i = nops - nout; i < nops; ++i)
+        for (int k = i + 1; k < nops; ++k)
+            if (ops[i] == ops[k])
+                return fail(RC_EINVAL, "%s: %s and %s alias each other (two outputs in one array)", who,
+                            names[i], names[k]);
+    const hipError_t e = rc_launch_gru_bwd(a, dtype, blend, reinterpret_cast<hipStream_t>(stream));
+    return hip_rc(e, blend ? "rc_gru_blend_backward: launch" : "rc_gru_gates_backward: launch");
+}
 }  // namespace
 
 extern "C" int rc_gru_gates(const void *z_pre, const void *r_pre, const void *cz, const void *cr,
@@ -975,4 +995,23 @@ extern "C" int rc_gru_blend(const void *z, const void *q_pre, const void *cq, co
     if (int rc = prep_gru(who, ops, names, 5, strides, dtype, N, C, HW, a, &empty)) return rc;
     if (empty) return RC_OK;
     return hip_rc(rc_launch_gru(a, dtype, true, reinterpret_cast<hipStream_t>(stream)), "rc_gru_blend: launch");
+}
+
+extern "C" int rc_gru_gates_backward(const void *g_z, const void *g_rh, const void *z, const void *r_pre,
+                                     const void *cr, const void *h, void *g_zpre, void *g_rpre, void *g_h,
+                                     const long *strides, int dtype, int N, int C, long HW, void *stream) {
+    void *const ops[9] = {const_cast<void *>(g_z), const_cast<void *>(g_rh), const_cast<void *>(z),
+                          const_cast<void *>(r_pre), const_cast<void *>(cr), const_cast<void *>(h),
+                          g_zpre, g_rpre, g_h};
+    const char *const names[9] = {"g_z", "g_rh", "z", "r_pre", "cr", "h", "g_zpre", "g_rpre", "g_h"};
+    return gru_backward("rc_gru_gates_backward", ops, names, 9, 3, strides, dtype, N, C, HW, false, stream);
+}
+
+extern "C" int rc_gru_blend_backward(const void *g_out, const void *z, const void *q_pre, const void *cq,
+                                     const void *h, void *g_z, void *g_qpre, void *g_h, const long *strides,
+                                     int dtype, int N, int C, long HW, void *stream) {
+    void *const ops[8] = {const_cast<void *>(g_out), const_cast<void *>(z), const_cast<void *>(q_pre),
+                          const_cast<void *>(cq), const_cast<void *>(h), g_z, g_qpre, g_h};
+    const char *const names[8] = {"g_out", "z", "q_pre", "cq", "h", "g_z", "g_qpre", "g_h"};
+    return gru_backward("rc_gru_blend_backward", ops, names, 8, 3, strides, dtype, N, C, HW, true, stream);
 }

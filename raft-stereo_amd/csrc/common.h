@@ -268,6 +268,17 @@ struct GruArgs {
     long long L;
     uint32_t J, units;        // set by the launcher: work units per row, and in all (< 2^32)
 };
+// rc_gru_gates_backward / rc_gru_blend_backward (gru_gates_bwd.hip): the same
+// with room for their 9 / 8 operands (GruArgs keeps its size, and with it the
+// forward kernels their code).
+struct GruBwdArgs {
+    GruOperand op[9];         // gates: g_z g_rh z r_pre cr h g_zpre g_rpre g_h
+                              // blend: g_out z q_pre cq h g_z g_qpre g_h
+    int N;
+    uint32_t O;
+    long long L;
+    uint32_t J, units;
+};
 
 // CUs of the device current at the first call, taken once: every GPU of a
 // node this project runs on is the same.  256 when the query fails.
@@ -326,6 +337,8 @@ bool rc_lookup_bwd_calls_fits(const rc::LookupBwdCallsArgs &a, int radius, int l
 hipError_t rc_launch_volume_bwd(const rc::BuildBwdArgs &a, hipStream_t s);
 // the ConvGRU gate / blend kernel on operands of element kind ek (gru_gates.hip)
 hipError_t rc_launch_gru(const rc::GruArgs &a, int ek, bool blend, hipStream_t s);
+// their backward kernels (gru_gates_bwd.hip)
+hipError_t rc_launch_gru_bwd(const rc::GruBwdArgs &a, int ek, bool blend, hipStream_t s);
 hipError_t rc_launch_convex_upsample(const float *flow, const float *mask, int N, int C, int H,
                                      int W, int factor, float *out, hipStream_t s);
 // grad_flow / grad_mask may be null (not computed); workspace is read only with grad_flow

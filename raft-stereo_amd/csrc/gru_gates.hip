@@ -27,30 +27,9 @@
 //     and subnormal a, NaN for NaN.
 // Aliasing: a unit reads all its inputs before it writes, and no other unit
 // touches its elements, so z_out may be z_pre and h_out may be h.
-#include "lookup_pair.h"   // out_cvt: the opaque copy keeps the last fp32 add and the convert two roundings
+#include "gru_gates.h"    // gru_sigmoid, GruPack, gru_load / gru_store, gru_width, gru_grid
 
 namespace rc {
-
-__device__ __forceinline__ float gru_sigmoid(float a) {
-    const float e = __builtin_amdgcn_exp2f(-a * 1.44269504088896340736f);
-    return __builtin_amdgcn_rcpf(1.0f + e);
-}
-
-template <class T, int V>
-struct alignas(sizeof(T) * V) GruPack {
-    T v[V];
-};
-
-template <class T, int V>
-__device__ __forceinline__ GruPack<T, V> gru_load(const GruOperand &op, long long n, long long o, long long i) {
-    return *reinterpret_cast<const GruPack<T, V> *>(static_cast<const T *>(op.p) + n * op.sn + o * op.so + i);
-}
-
-template <class T, int V>
-__device__ __forceinline__ void gru_store(const GruOperand &op, long long n, long long o, long long i,
-                                          const GruPack<T, V> &v) {
-    *reinterpret_cast<GruPack<T, V> *>(static_cast<T *>(op.p) + n * op.sn + o * op.so + i) = v;
-}
 
 // operands: 0 z_pre, 1 r_pre, 2 cz, 3 cr, 4 h, 5 z_out, 6 rh_out
 template <class T, int V>
@@ -99,28 +78,9 @@ __global__ __launch_bounds__(256) void gru_blend_kernel(GruArgs a) {
     }
 }
 
-// Largest access width (bytes: 16, 8 or one element) that the inner length,
-// every base address and every stride are whole multiples of.
-static int gru_width(const GruArgs &a, int nops, int esize) {
-    for (int bytes = 16; bytes > esize; bytes >>= 1) {
-        const long long v = bytes / esize;
-        bool ok = a.L % v == 0;
-        for (int k = 0; k < nops && ok; ++k)
-            ok = reinterpret_cast<uintptr_t>(a.op[k].p) % (uintptr_t)bytes == 0 && a.op[k].sn % v == 0 &&
-                 a.op[k].so % v == 0;
-        if (ok) return bytes;
-    }
-    return esize;
-}
-
 template <class T, int V>
 static void gru_launch_v(GruArgs a, bool blend, hipStream_t s) {
-    const long long units = (long long)a.N * a.O * (a.L / V);
-    a.J = (uint32_t)(a.L / V);
-    a.units = (uint32_t)units;
-    // capped one-dimensional grid, the rest by the grid-stride loop
-    const long long cap = (long long)device_cus() * 8, need = (units + 255) / 256;
-    const dim3 g((unsigned)(need < cap ? need : cap)), t(256);
+    const dim3 g = gru_grid(a, V), t(256);
     if (blend) hipLaunchKernelGGL((gru_blend_kernel<T, V>), g, t, 0, s, a);
     else hipLaunchKernelGGL((gru_gates_kernel<T, V>), g, t, 0, s, a);
 }

@@ -12,10 +12,17 @@ keeps the convolutions where they are and runs the rest as
   4. convq on that buffer,
   5. ``gru_blend``: the new hidden state.
 
-It is opt-in (``ConvGRU.fuse``, ``RAFTStereo(fuse_gru=True)``), inference-only
--- with a gradient being recorded ``fusable`` is false and the PyTorch ops run
--- and has no CPU fallback: the wrappers raise on tensors that are not on a
-HIP device.
+It is opt-in (``ConvGRU.fuse``, ``RAFTStereo(fuse_gru=True)``) and has no CPU
+fallback: the wrappers raise on tensors that are not on a HIP device.  With a
+gradient being recorded ``fusable`` is false and the PyTorch ops run, unless
+the training route is asked for as well (``ConvGRU.fuse_backward``,
+``RAFTStereo(fuse_gru_backward=True)``,
+``conv_gru_forward(differentiable=True)``): the same kernels inside two
+``torch.autograd.Function``s whose backward is one launch each
+(rc_gru_gates_backward, rc_gru_blend_backward; csrc/gru_gates_bwd.hip), the
+convolutions and the concatenations ordinary autograd ops.  That route keeps
+the [h, x] buffer, which the first convolution saves, and concatenates
+[r*h, x] into a second one.
 """
 import weakref
 
@@ -108,9 +115,11 @@ def _compute_dtype(gru, h):
     return gru.convz.weight.dtype
 
 
-def why_not_fusable(gru, h, cz, cr, cq, *x_list):
+def why_not_fusable(gru, h, cz, cr, cq, *x_list, differentiable=False):
     """None when ``conv_gru_forward`` can stand in for ``ConvGRU.forward`` on
-    these arguments, else the first reason why not, in words."""
+    these arguments, else the first reason why not, in words.
+    ``differentiable``: for ``conv_gru_forward(differentiable=True)``, which
+    a gradient being recorded does not stop; every other condition holds."""
     state = (h, cz, cr, cq)
     tensors = state + tuple(x_list)
     if not x_list or any(not isinstance(t, torch.Tensor) or t.dim() != 4 for t in tensors):
@@ -131,7 +140,7 @@ def why_not_fusable(gru, h, cz, cr, cq, *x_list):
                                                        for t in x_list):
         return "shapes do not match h's"
     cz_, cr_, cq_ = gru.convz, gru.convr, gru.convq
-    if torch.is_grad_enabled():
+    if torch.is_grad_enabled() and not differentiable:
         params = [p for c in (cz_, cr_, cq_) for p in (c.weight, c.bias) if p is not None]
         if any(t.requires_grad for t in tensors) or any(p.requires_grad for p in params):
             return "a gradient is being recorded (there is no backward kernel)"
@@ -152,15 +161,16 @@ def why_not_fusable(gru, h, cz, cr, cq, *x_list):
     return None
 
 
-def fusable(gru, h, cz, cr, cq, *x_list):
+def fusable(gru, h, cz, cr, cq, *x_list, differentiable=False):
     """Whether ``conv_gru_forward`` can stand in for ``ConvGRU.forward`` on
     these arguments: every tensor on one HIP device; h, cz, cr and cq of one
     dtype out of fp32 / fp16 / bf16, the one the gate convolutions compute in
     (the parts of x may be of other float dtypes only under autocast, where
     the convolution would cast them anyway); h, cz, cr and cq of one layout
     class with a mergeable H*W; convz and convr of one geometry; and no
-    gradient being recorded for any input or gate weight."""
-    return why_not_fusable(gru, h, cz, cr, cq, *x_list) is None
+    gradient being recorded for any input or gate weight -- the last one
+    only without ``differentiable``."""
+    return why_not_fusable(gru, h, cz, cr, cq, *x_list, differentiable=differentiable) is None
 
 
 def _check(name, ops, names):
@@ -193,6 +203,19 @@ def _empty_like_class(ref, cls):
     return torch.empty(ref.shape, dtype=ref.dtype, device=ref.device, memory_format=fmt)
 
 
+def _launch(name, ops, names):
+    """``_check`` and the call of entry point rc_<name> on the operands'
+    device and current stream."""
+    strides = _check(name, ops, names)
+    h = ops[0]
+    N, C, H, W = h.shape
+    with torch.cuda.device(h.device):
+        stream = torch.cuda.current_stream(h.device).cuda_stream or None
+        rc = getattr(_lib.lib(), "rc_" + name)(*(t.data_ptr() for t in ops), strides, _CODES[h.dtype], N, C, H * W,
+                                               stream)
+    _lib.check(rc, "rc_" + name)
+
+
 def gru_gates(z_pre, r_pre, cz, cr, h, z_out=None, rh_out=None):
     """z = sigmoid(z_pre + cz) and r*h with r = sigmoid(r_pre + cr), one launch
     (rc_gru_gates).  All operands (N, C, H, W) of one dtype and one layout
@@ -204,13 +227,8 @@ def gru_gates(z_pre, r_pre, cz, cr, h, z_out=None, rh_out=None):
         z_out = _empty_like_class(h, cls)
     if rh_out is None:
         rh_out = _empty_like_class(h, cls)
-    ops = (z_pre, r_pre, cz, cr, h, z_out, rh_out)
-    strides = _check("gru_gates", ops, ("z_pre", "r_pre", "cz", "cr", "h", "z_out", "rh_out"))
-    N, C, H, W = h.shape
-    with torch.cuda.device(h.device):
-        stream = torch.cuda.current_stream(h.device).cuda_stream or None
-        rc = _lib.lib().rc_gru_gates(*(t.data_ptr() for t in ops), strides, _CODES[h.dtype], N, C, H * W, stream)
-    _lib.check(rc, "rc_gru_gates")
+    _launch("gru_gates", (z_pre, r_pre, cz, cr, h, z_out, rh_out),
+            ("z_pre", "r_pre", "cz", "cr", "h", "z_out", "rh_out"))
     return z_out, rh_out
 
 
@@ -220,14 +238,38 @@ def gru_blend(z, q_pre, cq, h, h_out=None):
     when missing.  Returns h_out."""
     if h_out is None:
         h_out = _empty_like_class(h, _common_class((z, q_pre, cq, h)))
-    ops = (z, q_pre, cq, h, h_out)
-    strides = _check("gru_blend", ops, ("z", "q_pre", "cq", "h", "h_out"))
-    N, C, H, W = h.shape
-    with torch.cuda.device(h.device):
-        stream = torch.cuda.current_stream(h.device).cuda_stream or None
-        rc = _lib.lib().rc_gru_blend(*(t.data_ptr() for t in ops), strides, _CODES[h.dtype], N, C, H * W, stream)
-    _lib.check(rc, "rc_gru_blend")
+    _launch("gru_blend", (z, q_pre, cq, h, h_out), ("z", "q_pre", "cq", "h", "h_out"))
     return h_out
+
+
+def gru_gates_backward(g_z, g_rh, z, r_pre, cr, h, g_zpre=None, g_rpre=None, g_h=None):
+    """The gradients of ``gru_gates`` from those of its outputs, one launch
+    (rc_gru_gates_backward): g_zpre = g_z * (1 - z) * z, g_rpre = g_rh * h *
+    (1 - r) * r and g_h = g_rh * r, with r = sigmoid(r_pre + cr) recomputed.
+    g_zpre and g_rpre are the gradients of cz and cr as well.  Operands as for
+    ``gru_gates``; an output may be an input (``g_zpre`` over ``g_z``), the
+    outputs are three different tensors and are allocated when missing.
+    Returns (g_zpre, g_rpre, g_h)."""
+    ins = (g_z, g_rh, z, r_pre, cr, h)
+    cls = _common_class([t for t in ins if isinstance(t, torch.Tensor) and t.dim() == 4])
+    outs = [_empty_like_class(h, cls) if t is None else t for t in (g_zpre, g_rpre, g_h)]
+    _launch("gru_gates_backward", (*ins, *outs),
+            ("g_z", "g_rh", "z", "r_pre", "cr", "h", "g_zpre", "g_rpre", "g_h"))
+    return tuple(outs)
+
+
+def gru_blend_backward(g_out, z, q_pre, cq, h, g_z=None, g_qpre=None, g_h=None):
+    """The gradients of ``gru_blend`` from that of its output, one launch
+    (rc_gru_blend_backward): g_z = g_out * (q - h), g_qpre = g_out * z *
+    (1 - q*q) (the gradient of cq as well) and g_h = g_out * (1 - z), with
+    q = tanh(q_pre + cq) recomputed.  Operands as for ``gru_gates``; an output
+    may be an input (``g_h`` over ``g_out``), the outputs are three different
+    tensors and are allocated when missing.  Returns (g_z, g_qpre, g_h)."""
+    ins = (g_out, z, q_pre, cq, h)
+    cls = _common_class([t for t in ins if isinstance(t, torch.Tensor) and t.dim() == 4])
+    outs = [_empty_like_class(h, cls) if t is None else t for t in (g_z, g_qpre, g_h)]
+    _launch("gru_blend_backward", (*ins, *outs), ("g_out", "z", "q_pre", "cq", "h", "g_z", "g_qpre", "g_h"))
+    return tuple(outs)
 
 
 def _as_class(t, cls):
@@ -238,20 +280,101 @@ def _as_class(t, cls):
     return t.contiguous(memory_format=torch.contiguous_format if "planar" in cls else torch.channels_last)
 
 
-def conv_gru_forward(gru, h, cz, cr, cq, *x_list):
+def _one(cls):
+    return {"planar"} if "planar" in cls else {"interleaved"}
+
+
+class _GatesFn(torch.autograd.Function):
+    """(zr, cz, cr, h) -> (z, r*h) on rc_gru_gates; zr is the stacked z/r
+    convolution's output.  Saves z, the r_pre half of zr, cr and h; none of
+    them is written after this."""
+
+    @staticmethod
+    def forward(ctx, zr, cz, cr, h):
+        C = h.shape[1]
+        r_pre = zr[:, C:]
+        z, rh = gru_gates(zr[:, :C], r_pre, cz, cr, h)
+        ctx.save_for_backward(z, r_pre, cr, h)
+        return z, rh
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_z, g_rh):
+        z, r_pre, cr, h = ctx.saved_tensors
+        N, C, H, W = h.shape
+        cls = _one(_common_class((z, r_pre, cr, h)))
+        fmt = torch.contiguous_format if "planar" in cls else torch.channels_last
+        g_zr = torch.empty((N, 2 * C, H, W), dtype=h.dtype, device=h.device, memory_format=fmt)
+        g_zpre, g_rpre, g_h = gru_gates_backward(_as_class(g_z, cls), _as_class(g_rh, cls), z, r_pre, cr, h,
+                                                 g_zpre=g_zr[:, :C], g_rpre=g_zr[:, C:])
+        return g_zr, g_zpre, g_rpre, g_h
+
+
+class _BlendFn(torch.autograd.Function):
+    """(z, q_pre, cq, h) -> the new hidden state on rc_gru_blend; saves its
+    four inputs."""
+
+    @staticmethod
+    def forward(ctx, z, q_pre, cq, h):
+        ctx.save_for_backward(z, q_pre, cq, h)
+        return gru_blend(z, q_pre, cq, h)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        z, q_pre, cq, h = ctx.saved_tensors
+        cls = _one(_common_class((z, q_pre, cq, h)))
+        g_z, g_qpre, g_h = gru_blend_backward(_as_class(g_out, cls), z, q_pre, cq, h)
+        return g_z, g_qpre, g_qpre, g_h
+
+
+def _records_grad(gru, tensors):
+    """Whether autograd would record a gradient for an input or a gate weight."""
+    if not torch.is_grad_enabled():
+        return False
+    params = [p for c in (gru.convz, gru.convr, gru.convq) for p in (c.weight, c.bias) if p is not None]
+    return any(t.requires_grad for t in tensors) or any(p.requires_grad for p in params)
+
+
+def _conv_gru_train(gru, h, cz, cr, cq, x_list, cls):
+    """The training route of ``conv_gru_forward``: every step an autograd
+    node.  Each part is cast before the concatenation (``torch.cat(out=)``
+    records no gradient), and [r*h, x] is a second buffer: the stacked
+    convolution has saved [h, x]."""
+    dt = h.dtype
+    C = h.shape[1]
+    one = _one(cls)
+    fmt = torch.contiguous_format if "planar" in one else torch.channels_last
+    xs = [x.to(dt) for x in x_list]
+    hx = torch.cat([h, *xs], dim=1).contiguous(memory_format=fmt)
+    w, b, _ = _zr_conv(gru)
+    zr = _as_class(F.conv2d(hx, w, b, padding=gru.convz.padding, dilation=gru.convz.dilation), one)
+    z, rh = _GatesFn.apply(zr, cz, cr, h)
+    rx = torch.cat([rh, *xs], dim=1).contiguous(memory_format=fmt)
+    q = _as_class(gru.convq(rx), one)
+    return _BlendFn.apply(z, q, cq, h)
+
+
+def conv_gru_forward(gru, h, cz, cr, cq, *x_list, differentiable=False):
     """``ConvGRU.forward`` for arguments that are ``fusable``: the same three
     convolutions, one concatenation and two elementwise launches (module
-    docstring).  Returns the new hidden state, a new tensor in h's layout."""
+    docstring).  Returns the new hidden state, a new tensor in h's layout.
+    ``differentiable``: where a gradient is being recorded for an input or a
+    gate weight, record a first-order autograd graph whose glue is the two
+    backward kernels (arguments that are ``fusable(differentiable=True)``);
+    with nothing to record this is the inference route."""
     cls = _common_class((h, cz, cr, cq))
     if not cls:
         raise ValueError("conv_gru_forward: h, cz, cr and cq share no layout class (see gru.fusable)")
+    if differentiable and _records_grad(gru, (h, cz, cr, cq, *x_list)):
+        return _conv_gru_train(gru, h, cz, cr, cq, x_list, cls)
     dt = h.dtype
     N, C, H, W = h.shape
     Cx = sum(x.shape[1] for x in x_list)
     fmt = torch.contiguous_format if "planar" in cls else torch.channels_last
     hx = torch.empty((N, C + Cx, H, W), dtype=dt, device=h.device, memory_format=fmt)
     torch.cat([h, *x_list], dim=1, out=hx)
-    one = {"planar"} if "planar" in cls else {"interleaved"}
+    one = _one(cls)
     w, b, _ = _zr_conv_as(gru, dt)
     zr = _as_class(F.conv2d(hx, w, b, padding=gru.convz.padding, dilation=gru.convz.dilation), one)
     z = zr[:, :C]

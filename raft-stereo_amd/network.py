@@ -143,9 +143,15 @@ class ConvGRU(nn.Module):
     the glue between the three convolutions on the two gfx950 kernels of
     gru.py wherever ``gru.fusable`` holds -- HIP tensors of one dtype and
     layout class, no gradient being recorded; anything else takes the PyTorch
-    ops below, unchanged."""
+    ops below, unchanged.
+
+    ``fuse_backward`` (the same kind of attribute; needs ``fuse``): where only
+    the gradient being recorded stands in the way, take the fused route's
+    differentiable form, whose backward runs the glue on two more kernels
+    (``gru.conv_gru_forward(differentiable=True)``)."""
 
     fuse = False
+    fuse_backward = False
 
     def __init__(self, hidden_dim, input_dim, kernel_size=3):
         super().__init__()
@@ -156,6 +162,8 @@ class ConvGRU(nn.Module):
     def forward(self, h, cz, cr, cq, *x_list):
         if self.fuse and _gru.fusable(self, h, cz, cr, cq, *x_list):
             return _gru.conv_gru_forward(self, h, cz, cr, cq, *x_list)
+        if self.fuse and self.fuse_backward and _gru.fusable(self, h, cz, cr, cq, *x_list, differentiable=True):
+            return _gru.conv_gru_forward(self, h, cz, cr, cq, *x_list, differentiable=True)
         x = torch.cat(x_list, dim=1)
         hx = torch.cat([h, x], dim=1)
         z = torch.sigmoid(self.convz(hx) + cz)
@@ -245,7 +253,7 @@ class RAFTStereo(nn.Module):
     """model.py:335-383 with the correlation block pluggable (``corr_block``)."""
 
     def __init__(self, args, corr_block=None, fuse_convc1=False, fuse_step=False, corr_out_dtype=None,
-                 corr_pyramid_dtype=None, fuse_gru=False):
+                 corr_pyramid_dtype=None, fuse_gru=False, fuse_gru_backward=False):
         super().__init__()
         self.args = args
         # corr_out_dtype (DESIGN.md §3.2j): the lookup output's dtype (with
@@ -291,6 +299,14 @@ class RAFTStereo(nn.Module):
         self.fuse_gru = bool(fuse_gru)
         for name in ("gru08", "gru16", "gru32"):
             getattr(self.update_block, name).fuse = self.fuse_gru
+        # fuse_gru_backward: keep the fused route while a gradient is being
+        # recorded, with the glue's backward on two kernels of its own
+        # (gru.conv_gru_forward(differentiable=True)); training with fuse_gru.
+        if fuse_gru_backward and not fuse_gru:
+            raise ValueError("RAFTStereo: fuse_gru_backward=True needs fuse_gru=True")
+        self.fuse_gru_backward = bool(fuse_gru_backward)
+        for name in ("gru08", "gru16", "gru32"):
+            getattr(self.update_block, name).fuse_backward = self.fuse_gru_backward
 
     def initialize_flow(self, img):
         N, _, H, W = img.shape

@@ -17,8 +17,25 @@ PyTorch ops it replaces, alternated in one process.
            channels_last + MIOpen autotuning); host clock around synchronised
            forwards, per-round times, and the final disparities' difference.
 
+  train_kernels  forward + backward of the same glue: torch autograd of the
+           op sequence against the differentiable fused route's pieces (the
+           two autograd Functions of gru.py around rc_gru_gates / rc_gru_blend
+           and their backward kernels, with the two concatenations that route
+           keeps), convolutions excluded: the stacked z/r pre-activations and
+           q_pre are leaves, and the gradients the convolutions would send
+           into [h, x] and [r*h, x] are given tensors.  Same sizes, dtypes,
+           layouts and timing as ``kernels``.
+  train_step  one training step (forward, loss on every prediction,
+           backward) of RAFTStereo with and without the fused GRUs
+           (fuse_gru + fuse_gru_backward toggled on one model, alternated), at
+           B = 2, 320x720, 22 iterations -- a size whose activations fit next
+           to other jobs on one device -- in the settings of ``e2e``; host
+           clock around synchronised steps.
+
     python tools/gru_probe.py kernels [--out profiles/gru_gates.json]
     python tools/gru_probe.py e2e --setting bf16 [--rounds 3]
+    python tools/gru_probe.py train_kernels
+    python tools/gru_probe.py train_step --setting bf16_cl [--rounds 3]
 
 Each part merges its results into the --out file under its own key.
 """
@@ -125,6 +142,126 @@ def kernels_part(reps, rounds):
     return {"reps": reps, "rounds": rounds, "copy_rate_TB_per_s": COPY_RATE / 1e12, "rows": rows}
 
 
+def train_kernels_part(reps, rounds):
+    rows = []
+    N, C = 8, 128
+    for name, (H, W, parts) in SIZES.items():
+        for dt in (torch.float32, torch.bfloat16):
+            for cl in (False, True):
+                g = torch.Generator(device="cuda").manual_seed(0)
+                fmt = torch.channels_last if cl else torch.contiguous_format
+
+                def rnd(ch, grad=True):
+                    t = torch.randn(N, ch, H, W, device="cuda", generator=g).to(dt)
+                    return t.contiguous(memory_format=fmt).requires_grad_(grad)
+
+                h, zr, qp = torch.tanh(rnd(C, False)).requires_grad_(True), rnd(2 * C), rnd(C)
+                cz, cr, cq = rnd(C), rnd(C), rnd(C)
+                xs = [rnd(c) for c in parts]
+                # the unfused route has two convolutions: their outputs are two leaves
+                zp, rp = (t.detach().clone(memory_format=fmt).requires_grad_(True) for t in zr.split(C, dim=1))
+                leaves = [h, zr, zp, rp, qp, cz, cr, cq, *xs]
+                K = C + sum(parts)
+                g_out, g_hx, g_rx = rnd(C, False), rnd(K, False), rnd(K, False)
+
+                def step(forward):
+                    for t in leaves:
+                        t.grad = None
+                    out, hx, rx = forward()
+                    torch.autograd.backward([out, hx, rx], [g_out, g_hx, g_rx])
+
+                def torch_glue():
+                    x = torch.cat(xs, dim=1)
+                    hx = torch.cat([h, x], dim=1)
+                    z = torch.sigmoid(zp + cz)
+                    r = torch.sigmoid(rp + cr)
+                    rx = torch.cat([r * h, x], dim=1)
+                    q = torch.tanh(qp + cq)
+                    return (1 - z) * h + z * q, hx, rx
+
+                def fused_glue():
+                    hx = torch.cat([h, *xs], dim=1)
+                    z, rh = gru._GatesFn.apply(zr, cz, cr, h)
+                    rx = torch.cat([rh, *xs], dim=1)
+                    return gru._BlendFn.apply(z, qp, cq, h), hx, rx
+
+                z0, gq = torch.sigmoid(zr[:, :C] + cz).detach(), torch.empty_like(g_out)
+                gz, gh, gzr = torch.empty_like(g_out), torch.empty_like(g_out), torch.empty_like(zr.detach())
+                fns = {"torch_glue": lambda: step(torch_glue), "fused_glue": lambda: step(fused_glue),
+                       "gates_backward": lambda: gru.gru_gates_backward(g_out, g_rx[:, :C], z0, zr.detach()[:, C:],
+                                                                        cr.detach(), h.detach(), gzr[:, :C],
+                                                                        gzr[:, C:], gh),
+                       "blend_backward": lambda: gru.gru_blend_backward(g_out, z0, qp.detach(), cq.detach(),
+                                                                        h.detach(), gz, gq, gh)}
+                ms = alternate(fns, reps, rounds)
+                row = {"size": name, "shape": [N, C, H, W], "x_channels": list(parts),
+                       "dtype": str(dt).replace("torch.", ""), "layout": "NHWC" if cl else "NCHW"}
+                for k, v in ms.items():
+                    row[k] = summary(v)
+                elems = N * C * H * W * h.element_size()
+                for k, nops in (("gates_backward", 9), ("blend_backward", 8)):
+                    rate = nops * elems / (row[k]["median_us"] * 1e-6)
+                    row[k]["bytes"] = nops * elems
+                    row[k]["TB_per_s"] = rate / 1e12
+                    row[k]["of_copy_rate"] = rate / COPY_RATE
+                row["speedup"] = row["torch_glue"]["median_us"] / row["fused_glue"]["median_us"]
+                print(json.dumps(row), flush=True)
+                rows.append(row)
+    return {"reps": reps, "rounds": rounds, "copy_rate_TB_per_s": COPY_RATE / 1e12, "rows": rows}
+
+
+def train_step_part(setting, rounds, B=2, H=320, W=720, iters=22):
+    mixed, bench, cl = {"fp32": (False, False, False), "bf16": (True, False, False),
+                        "bf16_cl": (True, True, True)}[setting]
+    torch.backends.cudnn.benchmark = bench
+    torch.manual_seed(0)
+    args = StereoArgs(mixed_precision=mixed)
+    args.autocast_dtype = torch.bfloat16
+    model = RAFTStereo(args, fuse_gru=True, fuse_gru_backward=True).eval().cuda()
+    if cl:
+        model = model.to(memory_format=torch.channels_last)
+    grus = [getattr(model.update_block, n) for n in ("gru08", "gru16", "gru32")]
+    g = torch.Generator().manual_seed(1234)
+    img1 = (torch.rand(B, 3, H, W, generator=g) * 255).cuda()
+    img2 = torch.roll(img1, -8, dims=-1)
+
+    def step(fuse):
+        for m in grus:
+            m.fuse = m.fuse_backward = fuse
+        model.zero_grad(set_to_none=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        preds = model(img1, img2, iters=iters)
+        loss = sum(p[:, 0].float().abs().mean() for p in preds)
+        loss.backward()
+        torch.cuda.synchronize()
+        ms = (time.perf_counter() - t0) * 1e3
+        grad = torch.cat([p.grad.float().flatten() for p in model.parameters() if p.grad is not None])
+        return ms, loss.item(), grad
+
+    ms = {False: [], True: []}
+    last = {fuse: step(fuse) for fuse in (False, True)}       # warm-up: every shape of both routes
+    torch.cuda.reset_peak_memory_stats()
+    peak = {}
+    for _ in range(rounds):
+        for fuse in (False, True):
+            last[fuse] = step(fuse)
+            ms[fuse].append(last[fuse][0])
+            peak[fuse] = torch.cuda.max_memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+    gu, gf = last[False][2], last[True][2]
+    res = {"setting": setting, "mixed_bf16": mixed, "miopen_benchmark": bench, "channels_last": cl,
+           "shape": [B, H, W], "iters": iters, "rounds": rounds,
+           "unfused_ms": ms[False], "fused_ms": ms[True],
+           "unfused_median_ms": statistics.median(ms[False]), "fused_median_ms": statistics.median(ms[True]),
+           "unfused_peak_GiB": peak[False] / 2 ** 30, "fused_peak_GiB": peak[True] / 2 ** 30,
+           "loss_unfused": last[False][1], "loss_fused": last[True][1],
+           "grad_norm_err": ((gf - gu).abs().max() / gu.abs().max()).item()}
+    res["fused_over_unfused"] = res["fused_median_ms"] / res["unfused_median_ms"]
+    print(json.dumps(res), flush=True)
+    return res
+
+
 def e2e_part(setting, rounds, B=8, H=540, W=960, iters=32):
     mixed, bench, cl = {"fp32": (False, False, False), "bf16": (True, False, False),
                         "bf16_cl": (True, True, True)}[setting]
@@ -169,7 +306,7 @@ def e2e_part(setting, rounds, B=8, H=540, W=960, iters=32):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("part", choices=["kernels", "e2e"])
+    ap.add_argument("part", choices=["kernels", "e2e", "train_kernels", "train_step"])
     ap.add_argument("--setting", choices=["fp32", "bf16", "bf16_cl"], default="bf16")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=None)
@@ -179,6 +316,10 @@ def main():
         sys.exit("gru_probe: needs a HIP device (no CPU timing)")
     if a.part == "kernels":
         key, res = "kernels", kernels_part(a.reps, a.rounds or 7)
+    elif a.part == "train_kernels":
+        key, res = "train_kernels", train_kernels_part(a.reps, a.rounds or 7)
+    elif a.part == "train_step":
+        key, res = f"train_step_{a.setting}", train_step_part(a.setting, a.rounds or 3)
     else:
         key, res = f"e2e_{a.setting}", e2e_part(a.setting, a.rounds or 3)
     doc = {}
