@@ -60,6 +60,24 @@ def ctypes_void(v):
     return v if v else None
 
 
+def _launch(entry, device, *args):
+    """Every call into libraftcorr from this module: ``entry(*args, stream)``
+    with ``device`` current and its current stream as the trailing argument;
+    a non-zero return code raises (_lib.check).  On every lookup's host path:
+    kept to one frame (the stream as :func:`_stream` gives it, inline), and
+    torch is given the device's index, which it does not have to parse."""
+    # pool_level and build_backward come here with whatever device their
+    # tensors have: given a CPU device object torch raised this; given its
+    # index (None) it would pick the current GPU and the kernel a host pointer
+    if device.type != "cuda":
+        raise ValueError(f"Expected a cuda device, but got: {device}")
+    idx = device.index
+    with torch.cuda.device(idx):
+        rc = getattr(_lib.lib(), entry)(*args, torch.cuda.current_stream(idx).cuda_stream or None)
+    if rc:
+        _lib.check(rc, entry)
+
+
 def _require_hip(t, what):
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{what} must be a torch.Tensor")
@@ -138,18 +156,26 @@ def _prep_fmap(f, pyramid_dtype=None):
 _ROW_ALIGN_BYTES = 16
 
 
+def _padded(P, W, dtype, pad=True, shadow=False):
+    """(ld, elements, element size) of a stored level of P rows of width W: the
+    row stride, W rounded up to 16 bytes when ``pad``, and the size of its
+    allocation -- with ``shadow``, up to the end of the RC_SHADOW copy that
+    starts ``_lib.shadow_offset`` bytes (include/raftcorr.h) after the level."""
+    es = torch.tensor([], dtype=dtype).element_size()
+    per16 = _ROW_ALIGN_BYTES // es
+    ld = -(-W // per16) * per16 if pad else W
+    return ld, P * ld + (_lib.shadow_offset(P, ld, es) // es if shadow else 0), es
+
+
 def _level_buffer(P, W, dtype, device, pad, shadow=False):
     """(P, 1, 1, W) tensor whose rows start 16-byte aligned: a view of a
     (P, ld) buffer with ld = W rounded up to 16 bytes when ``pad`` (the
     kernels then store whole aligned vectors; the padding is never read).
-    ``shadow``: the allocation also holds the level's RC_SHADOW copy at
-    ``_lib.shadow_offset`` bytes (include/raftcorr.h); the view is the primary."""
-    es = torch.tensor([], dtype=dtype).element_size()
-    per16 = _ROW_ALIGN_BYTES // es
-    ld = -(-W // per16) * per16 if pad else W
+    ``shadow``: the allocation also holds the level's RC_SHADOW copy; the
+    view is the primary."""
+    ld, n, _ = _padded(P, W, dtype, pad, shadow)
     if shadow:
-        total = _lib.shadow_offset(P, ld, es) + P * ld * es
-        buf = torch.empty(-(-total // es), dtype=dtype, device=device)[:P * ld].view(P, ld)
+        buf = torch.empty(n, dtype=dtype, device=device)[:P * ld].view(P, ld)
     else:
         buf = torch.empty((P, ld), dtype=dtype, device=device)
     if ld == W:
@@ -174,9 +200,8 @@ def _shadow_flags(levels, pyr):
 def shadow_fits(P, W, dtype):
     """True when a level of width W and its RC_SHADOW copy fit the 4 GiB the
     pair kernel addresses with 32-bit buffer offsets."""
-    es = torch.tensor([], dtype=dtype).element_size()
-    ld = -(-W // (_ROW_ALIGN_BYTES // es)) * (_ROW_ALIGN_BYTES // es)
-    return _lib.shadow_offset(P, ld, es) + P * ld * es <= 0xFFFFFF00
+    _, n, es = _padded(P, W, dtype, shadow=True)
+    return n * es <= 0xFFFFFF00
 
 
 def _row_stride(t):
@@ -214,14 +239,12 @@ def build_pyramid(fmap1, fmap2, nbuf, pyramid_dtype=torch.float32, pad=True, ski
            for l in range(nbuf)]
     if P == 0:
         return pyr
-    with torch.cuda.device(f1.device):
-        rc = _lib.lib().rc_corr_build(
+    _launch("rc_corr_build", f1.device,
             f1.data_ptr(), f2.data_ptr(), _dtype_code(f1.dtype), B, D, H, W1, W2,
             _lib.ptr_array([None if t is None else t.data_ptr() for t in pyr]),
             _lib.long_array([W2 >> l if t is None else _row_stride(t) for l, t in enumerate(pyr)]),
             nbuf, _dtype_code(pyramid_dtype) | _shadow_flags(shadow, pyr) |
-            (_lib.RC_BUILD_EXACT_F32 if exact_f32 else 0), _stream(f1.device))
-    _lib.check(rc, "rc_corr_build")
+            (_lib.RC_BUILD_EXACT_F32 if exact_f32 else 0))
     return pyr
 
 
@@ -232,15 +255,16 @@ def pool_level(src):
     out = _level_buffer(P, W // 2, src.dtype, src.device, True)
     if P == 0:
         return out
-    with torch.cuda.device(src.device):
-        rc = _lib.lib().rc_corr_pool(src.data_ptr(), _row_stride(src), out.data_ptr(),
-                                     _row_stride(out), P, W, _dtype_code(src.dtype),
-                                     _stream(src.device))
-    _lib.check(rc, "rc_corr_pool")
+    _launch("rc_corr_pool", src.device, src.data_ptr(), _row_stride(src), out.data_ptr(),
+            _row_stride(out), P, W, _dtype_code(src.dtype))
     return out
 
 
-def _check_coords(pyramid, coords):
+def _check_coords(coords, rows, device):
+    """Check (B, 2, H, W1) fp32 lookup coordinates against a volume (or its
+    level gradients) of ``rows`` = B*H*W1 pixel rows on ``device``; returns
+    the x channel as the kernels read it (unit column stride, row stride W1)
+    and its batch stride."""
     _require_hip(coords, "coords")
     if coords.dim() != 4 or coords.shape[1] < 1:
         raise RuntimeError("CorrBlock1D: coords must be (B, 2, H, W1)")
@@ -249,11 +273,11 @@ def _check_coords(pyramid, coords):
             f"CorrBlock1D: coords dtype {coords.dtype} != float32 (grid_sample "
             "requires the grid dtype to match the volume, model.py:275)")
     B, _, H, W1 = coords.shape
-    if B * H * W1 != pyramid[0].shape[0]:
+    if B * H * W1 != rows:
         raise RuntimeError(
             f"CorrBlock1D: coords {tuple(coords.shape)} do not match the volume's "
-            f"{pyramid[0].shape[0]} rows (view at model.py:312)")
-    if coords.device != pyramid[0].device:
+            f"{rows} rows (view at model.py:312)")
+    if coords.device != device:
         raise RuntimeError("CorrBlock1D: coords and pyramid on different devices")
     x = coords[:, 0]
     if x.stride(2) != 1 or x.stride(1) != W1:
@@ -262,12 +286,48 @@ def _check_coords(pyramid, coords):
     return x, cbs
 
 
-def _level_args(pyramid, num_levels):
-    levels = [pyramid[i] for i in range(num_levels)]
-    levels = [t if t.stride(-1) == 1 and t.data_ptr() % 16 == 0 else t.contiguous() for t in levels]
-    return (levels, _lib.ptr_array([t.data_ptr() for t in levels]),
-            _lib.int_array([t.shape[-1] for t in levels]),
-            _lib.long_array([_row_stride(t) for t in levels]), _dtype_code(levels[0].dtype))
+def _lookup_args(num_levels, kind, store, shadow=False, W1=None, W2=None):
+    """``(keep-alive, ptrs, widths, lds, flags)``, the leading arguments of
+    every lookup entry point, from what a block stores:
+
+    ``"levels"``: rows, every level in ``store[:num_levels]`` read (the
+        per-level kernels);
+    ``"chain"``: rows that are the avg-pool chain of level 0; entries may be
+        None or missing (recomputed by the kernel, passed as NULL).
+        ``shadow``: levels built with their RC_SHADOW copy (build_pyramid's
+        ``shadow``); their flags are passed unless a level had to be copied;
+    ``"disparity"``: the RC_LAYOUT_DISPARITY levels {0: S_0, 2: S_2}, with
+        the fmap widths ``W1`` and ``W2``, which the tensors do not show;
+    ``"records"``: the RC_LAYOUT_RECORDS tensor, with ``W2``.
+    Callers keep these as a dict of keyword arguments."""
+    if kind == "records":
+        return (store,) + _records_args(store, W2) + (_lib.RC_BF16 | _lib.RC_LAYOUT_RECORDS,)
+    if kind == "disparity":
+        stored = [l for l in range(num_levels) if l in (0, 2)]
+        return (store, _lib.ptr_array([store[l].data_ptr() if l in stored else None for l in range(num_levels)]),
+                _lib.int_array([W2 >> l for l in range(num_levels)]),
+                _lib.long_array([_shear_ld(W1) if l in stored else W2 >> l for l in range(num_levels)]),
+                _lib.RC_F32 | _lib.RC_LAYOUT_DISPARITY)
+    # rows go to the kernels with unit column stride and 16-byte aligned:
+    # a level that is not is copied
+    if kind == "levels":
+        lv = [store[i] for i in range(num_levels)]
+        lv = [t if t.stride(-1) == 1 and t.data_ptr() % 16 == 0 else t.contiguous() for t in lv]
+        return (lv, _lib.ptr_array([t.data_ptr() for t in lv]), _lib.int_array([t.shape[-1] for t in lv]),
+                _lib.long_array([_row_stride(t) for t in lv]), _dtype_code(lv[0].dtype))
+    src = list(store[:num_levels]) + [None] * (num_levels - len(store))
+    lv = [None if t is None else
+          (t if t.stride(-1) == 1 and t.data_ptr() % 16 == 0 else t.contiguous())
+          for t in src]
+    shadow = _shadow_levels(shadow, num_levels) if all(a is b for a, b in zip(lv, src)) else ()
+    dt = lv[0].dtype
+    if any(t is not None and t.dtype != dt for t in lv):
+        raise TypeError("lookup_chain: pyramid levels of one dtype required")
+    W0 = lv[0].shape[-1]
+    return (lv, _lib.ptr_array([None if t is None else t.data_ptr() for t in lv]),
+            _lib.int_array([W0 >> i for i in range(num_levels)]),
+            _lib.long_array([W0 >> i if t is None else _row_stride(t) for i, t in enumerate(lv)]),
+            _dtype_code(dt) | _shadow_flags(shadow, lv))
 
 
 def _convc1_params(coords, cin, weight, bias):
@@ -290,42 +350,64 @@ def _convc1_params(coords, cin, weight, bias):
     return w, b
 
 
-def lookup_convc1(pyramid, coords, num_levels, radius, weight, bias=None, relu=True):
-    """Lookup fused with a 1x1 conv (+ReLU): relu(conv1x1(lookup(coords))),
-    i.e. BasicMotionEncoder's ``F.relu(self.convc1(corr))`` (model.py:199, :206)."""
-    x, cbs = _check_coords(pyramid, coords)
+def _lookup_out(B, C, H, W1, device, channels_last, dtype=None):
+    """(B, C, H, W1) lookup output, fp32 unless ``dtype`` (a checked
+    out_dtype) says otherwise; channels_last: NHWC memory order (the C-ABI's
+    RC_OUT_CHANNELS_LAST), same shape and values."""
+    dtype = torch.float32 if dtype is None else dtype
+    if channels_last:
+        return torch.empty((B, H, W1, C), dtype=dtype, device=device).permute(0, 3, 1, 2)
+    return torch.empty((B, C, H, W1), dtype=dtype, device=device)
+
+
+def _pair_layout(pyramid, num_levels):
+    """The pair kernel serves this request (include/raftcorr.h, chain_kind)."""
+    return num_levels == 2 or (num_levels == 4 and len(pyramid) > 2 and pyramid[2] is not None)
+
+
+def _pair_only(who, pyramid, num_levels, hint=""):
+    if not _pair_layout(pyramid, num_levels):
+        raise _lib.CorrLibError(f"{who}: the pair layout only (2 levels, or 4 levels with level 2 present){hint}")
+
+
+def _convc1_forward(pyramid, coords, num_levels, radius, weight, bias, relu, chain=False, shadow=False,
+                    od=None):
+    """The fused lookup + 1x1 conv (+ReLU), one launch.  Not ``chain``:
+    rc_corr_lookup_conv on levels 0 .. L-1 of a full pyramid, fp32 output
+    (``od``, a checked out_dtype, is a cast after it).  ``chain``:
+    rc_corr_lookup_chain_conv on the pair layout (``pyramid`` / ``shadow`` as
+    for :func:`lookup_chain`), which writes ``od`` itself."""
+    x, cbs = _check_coords(coords, pyramid[0].shape[0], pyramid[0].device)
     B, _, H, W1 = coords.shape
+    if chain:
+        _pair_only("lookup_chain_convc1", pyramid, num_levels, "; lookup_convc1 reads a full pyramid")
     w, b = _convc1_params(coords, num_levels * (2 * radius + 1), weight, bias)
     cout = w.shape[0]
-    out = torch.empty((B, cout, H, W1), dtype=torch.float32, device=coords.device)
-    if B * H * W1 == 0:
-        return out
-    keep, ptrs, widths, lds, dt = _level_args(pyramid, num_levels)
-    with torch.cuda.device(coords.device):
-        rc = _lib.lib().rc_corr_lookup_conv(
-            ptrs, widths, lds, dt, num_levels, radius, x.data_ptr(), cbs, B, H, W1,
-            w.data_ptr(), b.data_ptr() if b is not None else None, cout, int(relu),
-            out.data_ptr(), _stream(coords.device))
-    _lib.check(rc, "rc_corr_lookup_conv")
-    return out
+    out = torch.empty((B, cout, H, W1), dtype=od if chain and od is not None else torch.float32,
+                      device=coords.device)
+    if B * H * W1:
+        keep, ptrs, widths, lds, flags = _lookup_args(num_levels, "chain" if chain else "levels", pyramid,
+                                                      shadow=shadow)
+        _launch("rc_corr_lookup_chain_conv" if chain else "rc_corr_lookup_conv", coords.device,
+                ptrs, widths, lds, flags | (_out_flag(od) if chain else 0), num_levels, radius, x.data_ptr(),
+                cbs, B, H, W1, w.data_ptr(), b.data_ptr() if b is not None else None, cout, int(relu),
+                out.data_ptr())
+    return out if od is None else out.to(od)     # no copy where the kernel wrote od
 
 
-def lookup_convc1_backward(pyramid, coords, num_levels, radius, weight, bias, relu, grad_out,
-                           need_corr=True, need_weight=True, need_bias=True):
-    """Run rc_corr_lookup_conv_backward: the gradients of ``lookup_convc1`` for
-    ``grad_out`` (B, cout, H, W1).  Returns ``(grad_corr, grad_weight,
-    grad_bias)``: (B, L(2r+1), H, W1), (cout, L(2r+1)) and (cout,) fp32, None
-    where not asked for.  The lookup is recomputed from ``pyramid``; grad_corr
-    is what ``lookup_backward`` / ``lookup_backward_calls`` take as grad_out."""
-    x, cbs = _check_coords(pyramid, coords)
+def _convc1_backward(pyramid, coords, num_levels, radius, weight, bias, relu, grad_out,
+                     need_corr=True, need_weight=True, need_bias=True, chain=False, shadow=False):
+    """The gradients of :func:`_convc1_forward` for ``grad_out`` (B, cout, H,
+    W1), with the lookup recomputed from ``pyramid``: rc_corr_lookup_conv_backward
+    (not ``chain``), else rc_corr_lookup_chain_conv_backward on the pair layout."""
+    x, cbs = _check_coords(coords, pyramid[0].shape[0], pyramid[0].device)
     B, _, H, W1 = coords.shape
+    if chain:
+        _pair_only("lookup_chain_convc1_backward", pyramid, num_levels)
     cin = num_levels * (2 * radius + 1)
     dev = coords.device
-    w = weight.detach().reshape(weight.shape[0], -1).float().contiguous()
-    if w.shape[1] != cin:
-        raise RuntimeError(f"lookup_convc1: weight has {w.shape[1]} input channels, lookup gives {cin}")
+    w, b = _convc1_params(coords, cin, weight, bias)
     cout = w.shape[0]
-    b = bias.detach().float().contiguous() if bias is not None else None
     if tuple(grad_out.shape) != (B, cout, H, W1):
         raise RuntimeError(f"lookup_convc1: grad_out {tuple(grad_out.shape)} != {(B, cout, H, W1)}")
     if not (need_corr or need_weight or need_bias):
@@ -343,97 +425,30 @@ def lookup_convc1_backward(pyramid, coords, num_levels, radius, weight, bias, re
     # one partial sum per workgroup of 256 pixels, reduced by the second launch
     ws = (torch.empty(_lib.lookup_conv_bwd_ws(P, cout, cin), dtype=torch.float32, device=dev)
           if need_weight or need_bias else None)
-    keep, ptrs, widths, lds, dt = _level_args(pyramid, num_levels)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().rc_corr_lookup_conv_backward(
-            ptrs, widths, lds, dt, num_levels, radius, x.data_ptr(), cbs, B, H, W1,
+    keep, ptrs, widths, lds, flags = _lookup_args(num_levels, "chain" if chain else "levels", pyramid,
+                                                  shadow=shadow)
+    _launch("rc_corr_lookup_chain_conv_backward" if chain else "rc_corr_lookup_conv_backward", dev,
+            ptrs, widths, lds, flags, num_levels, radius, x.data_ptr(), cbs, B, H, W1,
             w.data_ptr(), b.data_ptr() if b is not None else None, cout, int(relu), g.data_ptr(),
-            *(t.data_ptr() if t is not None else None for t in (gc, gw, gb, ws)), _stream(dev))
-    _lib.check(rc, "rc_corr_lookup_conv_backward")
+            *(t.data_ptr() if t is not None else None for t in (gc, gw, gb, ws)))
     return gc, gw, gb
 
 
-def lookup(pyramid, coords, num_levels, radius):
-    """Run rc_corr_lookup on levels [0, num_levels) of ``pyramid``."""
-    x, cbs = _check_coords(pyramid, coords)
-    B, _, H, W1 = coords.shape
-    C = num_levels * (2 * radius + 1)
-    out = torch.empty((B, C, H, W1), dtype=torch.float32, device=coords.device)
-    if B * H * W1 == 0:
-        return out
-    keep, ptrs, widths, lds, dt = _level_args(pyramid, num_levels)
-    with torch.cuda.device(coords.device):
-        rc = _lib.lib().rc_corr_lookup(ptrs, widths, lds, dt, num_levels, radius, x.data_ptr(), cbs,
-                                       B, H, W1, out.data_ptr(), _stream(coords.device))
-    _lib.check(rc, "rc_corr_lookup")
-    return out
+def lookup_convc1(pyramid, coords, num_levels, radius, weight, bias=None, relu=True):
+    """Lookup fused with a 1x1 conv (+ReLU): relu(conv1x1(lookup(coords))),
+    i.e. BasicMotionEncoder's ``F.relu(self.convc1(corr))`` (model.py:199, :206)."""
+    return _convc1_forward(pyramid, coords, num_levels, radius, weight, bias, relu)
 
 
-def _chain_args(pyramid, num_levels, shadow=False):
-    """Pointer / width / stride arrays for the pool-chain kernels: the levels
-    present in ``pyramid`` (None = recomputed by the kernel, passed as NULL).
-    ``shadow``: levels built with their RC_SHADOW copy (build_pyramid's
-    ``shadow``); their flags are passed unless a level had to be copied."""
-    src = list(pyramid[:num_levels]) + [None] * (num_levels - len(pyramid))
-    lv = [None if t is None else
-          (t if t.stride(-1) == 1 and t.data_ptr() % 16 == 0 else t.contiguous())
-          for t in src]
-    shadow = _shadow_levels(shadow, num_levels) if all(a is b for a, b in zip(lv, src)) else ()
-    dt = lv[0].dtype
-    if any(t is not None and t.dtype != dt for t in lv):
-        raise TypeError("lookup_chain: pyramid levels of one dtype required")
-    W0 = lv[0].shape[-1]
-    ptrs = _lib.ptr_array([None if t is None else t.data_ptr() for t in lv])
-    widths = _lib.int_array([W0 >> i for i in range(num_levels)])
-    lds = _lib.long_array([W0 >> i if t is None else _row_stride(t) for i, t in enumerate(lv)])
-    return lv, ptrs, widths, lds, _dtype_code(dt) | _shadow_flags(shadow, lv)
-
-
-def _lookup_out(B, C, H, W1, device, channels_last, dtype=None):
-    """(B, C, H, W1) lookup output, fp32 unless ``dtype`` (a checked
-    out_dtype) says otherwise; channels_last: NHWC memory order (the C-ABI's
-    RC_OUT_CHANNELS_LAST), same shape and values."""
-    dtype = torch.float32 if dtype is None else dtype
-    if channels_last:
-        return torch.empty((B, H, W1, C), dtype=dtype, device=device).permute(0, 3, 1, 2)
-    return torch.empty((B, C, H, W1), dtype=dtype, device=device)
-
-
-def _pair_layout(pyramid, num_levels):
-    """The pair kernel serves this request (include/raftcorr.h, chain_kind)."""
-    return num_levels == 2 or (num_levels == 4 and len(pyramid) > 2 and pyramid[2] is not None)
-
-
-def lookup_chain(pyramid, coords, num_levels, radius, shadow=False, channels_last=False, out_dtype=None):
-    """rc_corr_lookup_chain: same result as :func:`lookup` for a pyramid whose
-    levels are the avg-pool chain of level 0 (what :func:`build_pyramid`
-    writes).  Entries may be None: with 2 levels, or 4 levels and level 2
-    present, the kernel reads levels 0 and 2 and derives 1 and 3; otherwise it
-    reads levels 0 and 1 and derives the rest (include/raftcorr.h).
-    ``out_dtype`` (torch.float16 / torch.bfloat16): the pair kernel writes the
-    output in that dtype (RC_OUT_F16 / RC_OUT_BF16); the level-1 chain writes
-    fp32 and the cast follows -- the same values either way."""
-    x, cbs = _check_coords(pyramid, coords)
-    B, _, H, W1 = coords.shape
-    od = _check_out_dtype(out_dtype)
-    pair = _pair_layout(pyramid, num_levels)
-    cl = channels_last and pair
-    out = _lookup_out(B, num_levels * (2 * radius + 1), H, W1, coords.device, cl, od if pair else None)
-    if B * H * W1 == 0:
-        return out if od is None else out.to(od)
-    keep, ptrs, widths, lds, dt = _chain_args(pyramid, num_levels, shadow)
-    if cl:
-        dt |= _lib.RC_OUT_CHANNELS_LAST
-    if pair:
-        dt |= _out_flag(od)
-    with torch.cuda.device(coords.device):
-        rc = _lib.lib().rc_corr_lookup_chain(
-            ptrs, widths, lds, dt, num_levels, radius, x.data_ptr(), cbs, B, H, W1,
-            out.data_ptr(), _stream(coords.device))
-    _lib.check(rc, "rc_corr_lookup_chain")
-    if channels_last and not cl:
-        out = out.contiguous(memory_format=torch.channels_last)
-    return out if od is None else out.to(od)     # no copy where the kernel wrote od
+def lookup_convc1_backward(pyramid, coords, num_levels, radius, weight, bias, relu, grad_out,
+                           need_corr=True, need_weight=True, need_bias=True):
+    """Run rc_corr_lookup_conv_backward: the gradients of ``lookup_convc1`` for
+    ``grad_out`` (B, cout, H, W1).  Returns ``(grad_corr, grad_weight,
+    grad_bias)``: (B, L(2r+1), H, W1), (cout, L(2r+1)) and (cout,) fp32, None
+    where not asked for.  The lookup is recomputed from ``pyramid``; grad_corr
+    is what ``lookup_backward`` / ``lookup_backward_calls`` take as grad_out."""
+    return _convc1_backward(pyramid, coords, num_levels, radius, weight, bias, relu, grad_out,
+                            need_corr, need_weight, need_bias)
 
 
 def lookup_chain_convc1(pyramid, coords, num_levels, radius, weight, bias=None, relu=True, shadow=False,
@@ -445,24 +460,7 @@ def lookup_chain_convc1(pyramid, coords, num_levels, radius, weight, bias=None, 
     bit.  ``out_dtype`` (torch.float16 / torch.bfloat16): the kernel writes
     the output in that dtype, ``fp32_result.to(out_dtype)`` bit for bit."""
     od = _check_out_dtype(out_dtype)
-    x, cbs = _check_coords(pyramid, coords)
-    B, _, H, W1 = coords.shape
-    if not _pair_layout(pyramid, num_levels):
-        raise _lib.CorrLibError("lookup_chain_convc1: the pair layout only (2 levels, or 4 levels with "
-                                "level 2 present); lookup_convc1 reads a full pyramid")
-    w, b = _convc1_params(coords, num_levels * (2 * radius + 1), weight, bias)
-    cout = w.shape[0]
-    out = torch.empty((B, cout, H, W1), dtype=torch.float32 if od is None else od, device=coords.device)
-    if B * H * W1 == 0:
-        return out
-    keep, ptrs, widths, lds, dt = _chain_args(pyramid, num_levels, shadow)
-    with torch.cuda.device(coords.device):
-        rc = _lib.lib().rc_corr_lookup_chain_conv(
-            ptrs, widths, lds, dt | _out_flag(od), num_levels, radius, x.data_ptr(), cbs, B, H, W1,
-            w.data_ptr(), b.data_ptr() if b is not None else None, cout, int(relu),
-            out.data_ptr(), _stream(coords.device))
-    _lib.check(rc, "rc_corr_lookup_chain_conv")
-    return out
+    return _convc1_forward(pyramid, coords, num_levels, radius, weight, bias, relu, True, shadow, od)
 
 
 def lookup_chain_convc1_backward(pyramid, coords, num_levels, radius, weight, bias, relu, grad_out,
@@ -471,39 +469,60 @@ def lookup_chain_convc1_backward(pyramid, coords, num_levels, radius, weight, bi
     the lookup recomputed from the pair layout (``pyramid`` / ``shadow`` as
     for :func:`lookup_chain_convc1`).  Same arguments and results -- bit for
     bit those of :func:`lookup_convc1_backward` on the full pyramid."""
-    x, cbs = _check_coords(pyramid, coords)
+    return _convc1_backward(pyramid, coords, num_levels, radius, weight, bias, relu, grad_out,
+                            need_corr, need_weight, need_bias, True, shadow)
+
+
+def lookup(pyramid, coords, num_levels, radius):
+    """Run rc_corr_lookup on levels [0, num_levels) of ``pyramid``."""
+    x, cbs = _check_coords(coords, pyramid[0].shape[0], pyramid[0].device)
     B, _, H, W1 = coords.shape
-    cin = num_levels * (2 * radius + 1)
-    dev = coords.device
-    if not _pair_layout(pyramid, num_levels):
-        raise _lib.CorrLibError("lookup_chain_convc1_backward: the pair layout only (2 levels, or 4 levels "
-                                "with level 2 present)")
-    w, b = _convc1_params(coords, cin, weight, bias)
-    cout = w.shape[0]
-    if tuple(grad_out.shape) != (B, cout, H, W1):
-        raise RuntimeError(f"lookup_convc1: grad_out {tuple(grad_out.shape)} != {(B, cout, H, W1)}")
-    if not (need_corr or need_weight or need_bias):
-        return None, None, None
-    g = grad_out.detach().float().contiguous()
-    P = B * H * W1
-    gc = torch.empty((B, cin, H, W1), dtype=torch.float32, device=dev) if need_corr else None
-    gw = torch.empty((cout, cin), dtype=torch.float32, device=dev) if need_weight else None
-    gb = torch.empty((cout,), dtype=torch.float32, device=dev) if need_bias else None
-    if P == 0:
-        for t in (gw, gb):
-            if t is not None:
-                t.zero_()
-        return gc, gw, gb
-    ws = (torch.empty(_lib.lookup_conv_bwd_ws(P, cout, cin), dtype=torch.float32, device=dev)
-          if need_weight or need_bias else None)
-    keep, ptrs, widths, lds, dt = _chain_args(pyramid, num_levels, shadow)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().rc_corr_lookup_chain_conv_backward(
-            ptrs, widths, lds, dt, num_levels, radius, x.data_ptr(), cbs, B, H, W1,
-            w.data_ptr(), b.data_ptr() if b is not None else None, cout, int(relu), g.data_ptr(),
-            *(t.data_ptr() if t is not None else None for t in (gc, gw, gb, ws)), _stream(dev))
-    _lib.check(rc, "rc_corr_lookup_chain_conv_backward")
-    return gc, gw, gb
+    C = num_levels * (2 * radius + 1)
+    out = torch.empty((B, C, H, W1), dtype=torch.float32, device=coords.device)
+    if B * H * W1 == 0:
+        return out
+    keep, ptrs, widths, lds, dt = _lookup_args(num_levels, "levels", pyramid)
+    _launch("rc_corr_lookup", coords.device, ptrs, widths, lds, dt, num_levels, radius, x.data_ptr(), cbs,
+            B, H, W1, out.data_ptr())
+    return out
+
+
+def _chain_lookup(rows, device, src, coords, num_levels, radius, direct, channels_last=False, out_dtype=None):
+    """The rc_corr_lookup_chain call of every layout: a volume of ``rows``
+    pixel rows on ``device``, stored as ``src`` says (the keyword arguments of
+    :func:`_lookup_args`).  ``direct``: the pair or the records kernel serves
+    the request and writes channels-last and ``out_dtype`` itself; otherwise
+    the kernel writes fp32 NCHW and the conversions follow -- the same values
+    either way."""
+    x, cbs = _check_coords(coords, rows, device)
+    B, _, H, W1 = coords.shape
+    od = _check_out_dtype(out_dtype)
+    cl = channels_last and direct
+    out = _lookup_out(B, num_levels * (2 * radius + 1), H, W1, coords.device, cl, od if direct else None)
+    if B * H * W1:
+        keep, ptrs, widths, lds, flags = _lookup_args(num_levels, **src)
+        if cl:
+            flags |= _lib.RC_OUT_CHANNELS_LAST
+        if direct:
+            flags |= _out_flag(od)
+        _launch("rc_corr_lookup_chain", coords.device, ptrs, widths, lds, flags, num_levels, radius,
+                x.data_ptr(), cbs, B, H, W1, out.data_ptr())
+        if channels_last and not cl:
+            out = out.contiguous(memory_format=torch.channels_last)
+    return out if od is None else out.to(od)     # no copy where the kernel wrote od
+
+
+def lookup_chain(pyramid, coords, num_levels, radius, shadow=False, channels_last=False, out_dtype=None):
+    """rc_corr_lookup_chain: same result as :func:`lookup` for a pyramid whose
+    levels are the avg-pool chain of level 0 (what :func:`build_pyramid`
+    writes).  Entries may be None: with 2 levels, or 4 levels and level 2
+    present, the kernel reads levels 0 and 2 and derives 1 and 3; otherwise it
+    reads levels 0 and 1 and derives the rest (include/raftcorr.h).
+    ``out_dtype`` (torch.float16 / torch.bfloat16): the pair kernel writes the
+    output in that dtype (RC_OUT_F16 / RC_OUT_BF16); the level-1 chain writes
+    fp32 and the cast follows -- the same values either way."""
+    return _chain_lookup(pyramid[0].shape[0], pyramid[0].device, dict(kind="chain", store=pyramid, shadow=shadow),
+                         coords, num_levels, radius, _pair_layout(pyramid, num_levels), channels_last, out_dtype)
 
 
 # ------------------------------------------------- disparity-major layout
@@ -548,11 +567,9 @@ def build_sheared(fmap1, fmap2, num_levels, exact_f32=False):
     nbuf = 3 if num_levels == 4 else 1
     ptrs = [sh[0].data_ptr(), None, sh[2].data_ptr()] if nbuf == 3 else [sh[0].data_ptr()]
     lds = [ld, W2 >> 1, ld][:nbuf]
-    with torch.cuda.device(f1.device):
-        rc = _lib.lib().rc_corr_build(
+    _launch("rc_corr_build", f1.device,
             f1.data_ptr(), f2.data_ptr(), _lib.RC_F32, B, D, H, W1, W2, _lib.ptr_array(ptrs),
-            _lib.long_array(lds), nbuf, _lib.RC_F32 | _lib.RC_LAYOUT_DISPARITY, _stream(f1.device))
-    _lib.check(rc, "rc_corr_build")
+            _lib.long_array(lds), nbuf, _lib.RC_F32 | _lib.RC_LAYOUT_DISPARITY)
     return sh
 
 
@@ -567,40 +584,6 @@ def unshear_level(S, l, B, H, W1, W2):
     rows = S.view(B * H, K, ld)[:, kk, w1[:, None].expand(W1, W)]
     out = _level_buffer(B * H * W1, W, torch.float32, S.device, True)
     out.copy_(rows.reshape(B * H * W1, 1, 1, W))
-    return out
-
-
-def lookup_sheared(sheared, coords, num_levels, radius, W2):
-    """rc_corr_lookup_chain with RC_LAYOUT_DISPARITY: the pair kernel's
-    results (bit for bit) from the disparity-major levels."""
-    _require_hip(coords, "coords")
-    if coords.dim() != 4 or coords.shape[1] < 1:
-        raise RuntimeError("CorrBlock1D: coords must be (B, 2, H, W1)")
-    if coords.dtype != torch.float32:
-        raise RuntimeError(f"CorrBlock1D: coords dtype {coords.dtype} != float32 (model.py:275)")
-    B, _, H, W1 = coords.shape
-    ld = _shear_ld(W1)
-    if B * H * _lib.shear_rows(W2, W1, 0) * ld != sheared[0].numel():
-        raise RuntimeError(f"CorrBlock1D: coords {tuple(coords.shape)} do not match the volume "
-                           "(view at model.py:312)")
-    if coords.device != sheared[0].device:
-        raise RuntimeError("CorrBlock1D: coords and pyramid on different devices")
-    x = coords[:, 0]
-    if x.stride(2) != 1 or x.stride(1) != W1:
-        x = x.contiguous()
-    cbs = x.stride(0) if B > 1 else H * W1
-    out = torch.empty((B, num_levels * (2 * radius + 1), H, W1), dtype=torch.float32, device=coords.device)
-    if B * H * W1 == 0:
-        return out
-    ptrs = [sheared.get(l) if l in (0, 2) else None for l in range(num_levels)]
-    ptrs = _lib.ptr_array([None if t is None else t.data_ptr() for t in ptrs])
-    widths = _lib.int_array([W2 >> l for l in range(num_levels)])
-    lds = _lib.long_array([ld if l in (0, 2) else W2 >> l for l in range(num_levels)])
-    with torch.cuda.device(coords.device):
-        rc = _lib.lib().rc_corr_lookup_chain(
-            ptrs, widths, lds, _lib.RC_F32 | _lib.RC_LAYOUT_DISPARITY, num_levels, radius, x.data_ptr(),
-            cbs, B, H, W1, out.data_ptr(), _stream(coords.device))
-    _lib.check(rc, "rc_corr_lookup_chain")
     return out
 
 
@@ -654,12 +637,10 @@ def build_records(fmap1, fmap2):
     rec = torch.empty((B * H * W1, NR, _lib.RC_REC_SLOTS), dtype=torch.bfloat16, device=f1.device)
     if B * H * W1 == 0:
         return rec
-    with torch.cuda.device(f1.device):
-        rc = _lib.lib().rc_corr_build(
+    _launch("rc_corr_build", f1.device,
             f1.data_ptr(), f2.data_ptr(), _lib.RC_BF16, B, D, H, W1, W2,
             _lib.ptr_array([rec.data_ptr(), None, None]), _lib.long_array([W2, W2 >> 1, W2 >> 2]), 3,
-            _lib.RC_BF16 | _lib.RC_LAYOUT_RECORDS, _stream(f1.device))
-    _lib.check(rc, "rc_corr_build")
+            _lib.RC_BF16 | _lib.RC_LAYOUT_RECORDS)
     return rec
 
 
@@ -691,42 +672,12 @@ def _records_args(rec, W2):
     return ptrs, widths, lds
 
 
-def _check_records_coords(rec, coords):
-    _require_hip(coords, "coords")
-    if coords.dim() != 4 or coords.shape[1] < 1:
-        raise RuntimeError("CorrBlock1D: coords must be (B, 2, H, W1)")
-    if coords.dtype != torch.float32:
-        raise RuntimeError(f"CorrBlock1D: coords dtype {coords.dtype} != float32 (model.py:275)")
-    B, _, H, W1 = coords.shape
-    if B * H * W1 != rec.shape[0]:
-        raise RuntimeError(f"CorrBlock1D: coords {tuple(coords.shape)} do not match the volume's "
-                           f"{rec.shape[0]} rows (view at model.py:312)")
-    if coords.device != rec.device:
-        raise RuntimeError("CorrBlock1D: coords and pyramid on different devices")
-
-
 def lookup_records(rec, coords, radius, W2, channels_last=False, out_dtype=None):
     """rc_corr_lookup_chain with RC_LAYOUT_RECORDS: the pair kernel's
     results (bit for bit) from the records, one 128-B line per pixel.
     ``out_dtype``: torch.float16 / torch.bfloat16 output, written by the kernel."""
-    _check_records_coords(rec, coords)
-    B, _, H, W1 = coords.shape
-    x = coords[:, 0]
-    if x.stride(2) != 1 or x.stride(1) != W1:
-        x = x.contiguous()
-    cbs = x.stride(0) if B > 1 else H * W1
-    od = _check_out_dtype(out_dtype)
-    out = _lookup_out(B, 4 * (2 * radius + 1), H, W1, coords.device, channels_last, od)
-    if B * H * W1 == 0:
-        return out
-    ptrs, widths, lds = _records_args(rec, W2)
-    dt = (_lib.RC_BF16 | _lib.RC_LAYOUT_RECORDS | (_lib.RC_OUT_CHANNELS_LAST if channels_last else 0)
-          | _out_flag(od))
-    with torch.cuda.device(coords.device):
-        rc = _lib.lib().rc_corr_lookup_chain(ptrs, widths, lds, dt, 4, radius, x.data_ptr(), cbs, B, H, W1,
-                                             out.data_ptr(), _stream(coords.device))
-    _lib.check(rc, "rc_corr_lookup_chain")
-    return out
+    return _chain_lookup(rec.shape[0], rec.device, dict(kind="records", store=rec, W2=W2), coords, 4, radius,
+                         True, channels_last, out_dtype)
 
 
 # ----------------------------------------------------------------- backward
@@ -755,10 +706,9 @@ def grad_buffers(P, widths, device, pair=False, shadow=(), zero=True):
         if pair and l % 2 == 1:
             bufs.append(None)
             continue
-        ld = -(-W // 4) * 4
+        ld, n, _ = _padded(P, W, torch.float32, shadow=l in shadow)
         if l in shadow:
-            total = _lib.shadow_offset(P, ld, 4) + P * ld * 4
-            buf = torch.zeros(total // 4, dtype=torch.float32, device=device)[:P * ld].view(P, ld)
+            buf = torch.zeros(n, dtype=torch.float32, device=device)[:P * ld].view(P, ld)
         elif zero:
             buf = torch.zeros((P, ld), dtype=torch.float32, device=device)
         else:
@@ -772,6 +722,14 @@ def _grad_shadow_flags(grads):
     return sum(_lib.shadow_level(l) for l in getattr(grads, "shadow", ()))
 
 
+def _grad_args(grads, widths):
+    """(ptrs, lds) of level-gradient buffers for the backward entry points; a
+    level that is None (folded into its neighbour by the pair layout) goes as
+    NULL with its width as row stride."""
+    return (_lib.ptr_array([None if g is None else g.data_ptr() for g in grads]),
+            _lib.long_array([W if g is None else g.stride(0) for g, W in zip(grads, widths)]))
+
+
 def _pair_grads_ok(num_levels, radius, W0):
     return num_levels in (2, 4) and 1 <= radius <= 4 and W0 <= 65536
 
@@ -780,23 +738,17 @@ def lookup_backward(grads, coords, grad_out, num_levels, radius):
     """rc_corr_lookup_backward: accumulate d(lookup)/d(level i) . grad_out into
     ``grads`` (from :func:`grad_buffers`) -- grid_sample's input gradient
     (model.py:275) for every level and tap of the lookup at ``coords``."""
-    x, cbs = _check_coords(grads, coords)
+    x, cbs = _check_coords(coords, grads[0].shape[0], grads[0].device)
     B, _, H, W1 = coords.shape
     if B * H * W1 == 0:
         return
     go = grad_out.detach().float().contiguous()
     if go.shape != (B, num_levels * (2 * radius + 1), H, W1):
         raise RuntimeError(f"lookup_backward: grad_out shape {tuple(go.shape)}")
-    W0 = grads[0].shape[-1]
-    g = [grads[i] for i in range(num_levels)]
-    with torch.cuda.device(coords.device):
-        rc = _lib.lib().rc_corr_lookup_backward(
-            _lib.ptr_array([None if t is None else t.data_ptr() for t in g]),
-            _lib.int_array([W0 >> i for i in range(num_levels)]),
-            _lib.long_array([W0 >> i if t is None else t.stride(0) for i, t in enumerate(g)]),
-            num_levels | _grad_shadow_flags(grads), radius, x.data_ptr(), cbs, B, H, W1, go.data_ptr(),
-            _stream(coords.device))
-    _lib.check(rc, "rc_corr_lookup_backward")
+    widths = [grads[0].shape[-1] >> i for i in range(num_levels)]
+    ptrs, lds = _grad_args([grads[i] for i in range(num_levels)], widths)
+    _launch("rc_corr_lookup_backward", coords.device, ptrs, _lib.int_array(widths), lds,
+            num_levels | _grad_shadow_flags(grads), radius, x.data_ptr(), cbs, B, H, W1, go.data_ptr())
 
 
 def lookup_backward_calls(grads, coords_list, grad_out_list, num_levels, radius, overwrite=False):
@@ -819,7 +771,7 @@ def lookup_backward_calls(grads, coords_list, grad_out_list, num_levels, radius,
         return
     xs, cbss, gos = [], [], []
     for coords, grad_out in zip(coords_list, grad_out_list):
-        x, cbs = _check_coords(grads, coords)
+        x, cbs = _check_coords(coords, grads[0].shape[0], grads[0].device)
         B, _, H, W1 = coords.shape
         go = grad_out.detach().float().contiguous()
         if go.shape != (B, num_levels * (2 * radius + 1), H, W1):
@@ -832,18 +784,12 @@ def lookup_backward_calls(grads, coords_list, grad_out_list, num_levels, radius,
         raise RuntimeError("lookup_backward_calls: every call needs the same coords shape")
     if B * H * W1 == 0:
         return
-    W0 = grads[0].shape[-1]
-    g = [grads[i] for i in range(num_levels)]
-    flags = num_levels | (_lib.RC_GRAD_OVERWRITE if overwrite else 0)
-    with torch.cuda.device(coords_list[0].device):
-        rc = _lib.lib().rc_corr_lookup_backward_calls(
-            _lib.ptr_array([None if t is None else t.data_ptr() for t in g]),
-            _lib.int_array([W0 >> i for i in range(num_levels)]),
-            _lib.long_array([W0 >> i if t is None else t.stride(0) for i, t in enumerate(g)]),
-            flags, radius, len(xs), _lib.ptr_array([x.data_ptr() for x in xs]),
-            _lib.long_array(cbss), B, H, W1, _lib.ptr_array([go.data_ptr() for go in gos]),
-            _stream(coords_list[0].device))
-    _lib.check(rc, "rc_corr_lookup_backward_calls")
+    widths = [grads[0].shape[-1] >> i for i in range(num_levels)]
+    ptrs, lds = _grad_args([grads[i] for i in range(num_levels)], widths)
+    _launch("rc_corr_lookup_backward_calls", coords_list[0].device, ptrs, _lib.int_array(widths), lds,
+            num_levels | (_lib.RC_GRAD_OVERWRITE if overwrite else 0), radius, len(xs),
+            _lib.ptr_array([x.data_ptr() for x in xs]), _lib.long_array(cbss), B, H, W1,
+            _lib.ptr_array([go.data_ptr() for go in gos]))
 
 
 def build_backward(fmap1, fmap2, grads, exact_f32=False):
@@ -862,14 +808,10 @@ def build_backward(fmap1, fmap2, grads, exact_f32=False):
     flags = _grad_shadow_flags(grads)
     if len(grads) > 1 and grads[1] is None:
         grads = [grads[0], None, grads[2]] if len(grads) > 2 else [grads[0]]
-    with torch.cuda.device(f1.device):
-        rc = _lib.lib().rc_corr_build_backward(
+    ptrs, lds = _grad_args(grads, [W2 >> l for l in range(len(grads))])
+    _launch("rc_corr_build_backward", f1.device,
             f1.data_ptr(), f2.data_ptr(), _lib.RC_F32 | (_lib.RC_BUILD_EXACT_F32 if exact_f32 else 0),
-            B, D, H, W1, W2,
-            _lib.ptr_array([None if g is None else g.data_ptr() for g in grads]),
-            _lib.long_array([W2 >> l if g is None else g.stride(0) for l, g in enumerate(grads)]),
-            len(grads) | flags, df1.data_ptr(), df2.data_ptr(), _stream(f1.device))
-    _lib.check(rc, "rc_corr_build_backward")
+            B, D, H, W1, W2, ptrs, lds, len(grads) | flags, df1.data_ptr(), df2.data_ptr())
     return df1, df2
 
 
@@ -1046,11 +988,8 @@ class _LookupConvFn(torch.autograd.Function):
         ctx.state = state if token is not None else None
         ctx.levels, ctx.cfg, ctx.shadow = levels, (num_levels, radius, relu), shadow
         ctx.save_for_backward(coords, weight, bias)
-        if shadow is not None:
-            return lookup_chain_convc1(levels, coords, num_levels, radius, weight, bias, relu, shadow,
-                                       out_dtype)
-        out = lookup_convc1(levels, coords, num_levels, radius, weight, bias, relu)
-        return out if out_dtype is None else out.to(out_dtype)
+        return _convc1_forward(levels, coords, num_levels, radius, weight, bias, relu, shadow is not None,
+                               shadow, out_dtype)
 
     @staticmethod
     @once_differentiable
@@ -1060,19 +999,30 @@ class _LookupConvFn(torch.autograd.Function):
         need_corr = ctx.state is not None
         need_w = ctx.needs_input_grad[2]
         need_b = bias is not None and ctx.needs_input_grad[3]
-        if ctx.shadow is not None:
-            gc, gw, gb = lookup_chain_convc1_backward(ctx.levels, coords, num_levels, radius, weight, bias,
-                                                      relu, grad_out.float(), need_corr, need_w, need_b,
-                                                      shadow=ctx.shadow)
-        else:
-            gc, gw, gb = lookup_convc1_backward(ctx.levels, coords, num_levels, radius, weight, bias, relu,
-                                                grad_out.float(), need_corr, need_w, need_b)
+        gc, gw, gb = _convc1_backward(ctx.levels, coords, num_levels, radius, weight, bias, relu,
+                                      grad_out.float(), need_corr, need_w, need_b, ctx.shadow is not None,
+                                      ctx.shadow)
         token_grad = None
         if need_corr:
             ctx.state.accumulate(coords, gc)
             token_grad = ctx.state.token_grad(coords.device)
         return (token_grad, None, gw.view(weight.shape).to(weight.dtype) if need_w else None,
                 gb.view(bias.shape).to(bias.dtype) if need_b else None) + (None,) * 7
+
+
+# The opt-in layouts of CorrBlock1D: default pyramid dtype, why-not function,
+# the constructor options each refuses and with what text, the attribute that
+# holds what the build returns, and the build (fmap1, fmap2, num_levels).
+_LAYOUT_OPTIONS = ("low_latency", "shadow", "grad_shadow", "exact_f32", "eager")
+_LAYOUTS = {
+    "disparity": (torch.float32, shear_supported, ("channels_last",) + _LAYOUT_OPTIONS,
+                  "the default options only (NCHW output, no low_latency, shadow, grad_shadow, "
+                  "exact_f32 or eager levels)", "_sheared", build_sheared),
+    "records": (torch.bfloat16, records_supported, _LAYOUT_OPTIONS,
+                "no low_latency, shadow, grad_shadow, exact_f32 or eager levels (the records replace "
+                "the stored rows and their shadow copies)", "_records",
+                lambda fmap1, fmap2, num_levels: build_records(fmap1, fmap2)),
+}
 
 
 class CorrBlock1D:
@@ -1151,23 +1101,33 @@ class CorrBlock1D:
         self.layout = layout
         self._sheared = None
         self._records = None
-        if layout == "disparity":
-            self._init_sheared(fmap1, fmap2, num_levels, radius, pyramid_dtype, lazy_levels, shadow,
-                               channels_last, low_latency, grad_shadow, exact_f32, grad_deferred)
-            return
-        if layout == "records":
-            self._init_records(fmap1, fmap2, num_levels, radius, pyramid_dtype, lazy_levels, shadow,
-                               channels_last, low_latency, grad_shadow, exact_f32, grad_deferred)
-            return
         # lookup outputs in NHWC memory order (torch.channels_last): same
         # shape and values; written by the pair kernel as contiguous per-wave
         # runs instead of one 256-B piece per channel plane
         self.channels_last = bool(channels_last)
+        if layout != "rows":
+            # the opt-in layouts replace the stored rows and their shadow
+            # copies: one build, nothing lazy, the pair gradient layout
+            default_dtype, supported, refused, refused_text, attr, build = _LAYOUTS[layout]
+            if pyramid_dtype is None:
+                pyramid_dtype = default_dtype
+            why = supported(fmap1, fmap2, num_levels, radius, pyramid_dtype)
+            asked = dict(channels_last=channels_last, low_latency=low_latency, shadow=shadow,
+                         grad_shadow=grad_shadow, exact_f32=exact_f32, eager=lazy_levels is False)
+            if why is None and any(asked[o] for o in refused):
+                why = refused_text
+            if why is not None:
+                raise ValueError(f"CorrBlock1D(layout={layout!r}): {why}")
+            self.pyramid_dtype = pyramid_dtype
+            self._chain, self._shadow = True, frozenset()
+            with torch.no_grad():
+                setattr(self, attr, build(fmap1, fmap2, num_levels))
+            self._finish(fmap1, fmap2, _check_fmaps(fmap1, fmap2), [], None, grad_deferred, False)
+            return
         if pyramid_dtype is None:
             low = fmap1.dtype in (torch.bfloat16, torch.float16)
             pyramid_dtype = torch.bfloat16 if low else torch.float32
         self.pyramid_dtype = pyramid_dtype
-        grad = torch.is_grad_enabled() and (fmap1.requires_grad or fmap2.requires_grad)
         B, D, H, W1, W2 = _check_fmaps(fmap1, fmap2)
         if num_levels < 1 or (W2 >> num_levels) < 1:
             raise RuntimeError(
@@ -1230,65 +1190,23 @@ class CorrBlock1D:
                 self._shadow = self._shadow - frozenset(too_big)
             # exact_f32: the exact fp32 MFMA volume kernel instead of the
             # split-bf16 default (both fp32-accurate)
-            self._levels = build_pyramid(fmap1, fmap2, nbuf, pyramid_dtype, skip=skip,
-                                         shadow=self._shadow, exact_f32=exact_f32)
-            self._levels += [None] * (num_levels + 1 - nbuf)
-        self._state = self._token = None
-        if grad:
-            self._state = _GradState(B * H * W1, [W2 >> i for i in range(num_levels)],
-                                     fmap1.device, num_levels, radius, grad_shadow,
-                                     deferred=grad_deferred, exact_f32=exact_f32)
-            self._token = _BuildFn.apply(fmap1, fmap2, self._state)
+            levels = build_pyramid(fmap1, fmap2, nbuf, pyramid_dtype, skip=skip,
+                                   shadow=self._shadow, exact_f32=exact_f32)
+        self._finish(fmap1, fmap2, (B, D, H, W1, W2), levels, grad_shadow, grad_deferred, exact_f32)
 
-    def _init_sheared(self, fmap1, fmap2, num_levels, radius, pyramid_dtype, lazy_levels, shadow,
-                      channels_last, low_latency, grad_shadow, exact_f32, grad_deferred):
-        if pyramid_dtype is None:
-            pyramid_dtype = torch.float32
-        why = shear_supported(fmap1, fmap2, num_levels, radius, pyramid_dtype)
-        if why is None and (channels_last or low_latency or shadow or grad_shadow or exact_f32
-                            or lazy_levels is False):
-            why = ("the default options only (NCHW output, no low_latency, shadow, grad_shadow, "
-                   "exact_f32 or eager levels)")
-        if why is not None:
-            raise ValueError(f"CorrBlock1D(layout='disparity'): {why}")
-        self.pyramid_dtype = pyramid_dtype
-        self.channels_last = False
-        B, D, H, W1, W2 = _check_fmaps(fmap1, fmap2)
+    def _finish(self, fmap1, fmap2, shape, levels, grad_shadow, grad_deferred, exact_f32):
+        """The constructor's tail for every layout: ``levels`` are the rows
+        the build stored (the others stay None until ``corr_pyramid`` is
+        read); with gradients wanted, the shared level-gradient state and the
+        build's autograd node."""
+        B, D, H, W1, W2 = shape
+        L = self.num_levels
         self._shape = (B, H, W1, W2)
-        self._chain, self._shadow = True, frozenset()
-        grad = torch.is_grad_enabled() and (fmap1.requires_grad or fmap2.requires_grad)
-        with torch.no_grad():
-            self._sheared = build_sheared(fmap1, fmap2, num_levels)
-        self._levels = [None] * (num_levels + 1)
+        self._levels = levels + [None] * (L + 1 - len(levels))
         self._state = self._token = None
-        if grad:
-            self._state = _GradState(B * H * W1, [W2 >> i for i in range(num_levels)], fmap1.device,
-                                     num_levels, radius, None, deferred=grad_deferred)
-            self._token = _BuildFn.apply(fmap1, fmap2, self._state)
-
-    def _init_records(self, fmap1, fmap2, num_levels, radius, pyramid_dtype, lazy_levels, shadow,
-                      channels_last, low_latency, grad_shadow, exact_f32, grad_deferred):
-        if pyramid_dtype is None:
-            pyramid_dtype = torch.bfloat16
-        why = records_supported(fmap1, fmap2, num_levels, radius, pyramid_dtype)
-        if why is None and (low_latency or shadow or grad_shadow or exact_f32 or lazy_levels is False):
-            why = ("no low_latency, shadow, grad_shadow, exact_f32 or eager levels (the records replace "
-                   "the stored rows and their shadow copies)")
-        if why is not None:
-            raise ValueError(f"CorrBlock1D(layout='records'): {why}")
-        self.pyramid_dtype = pyramid_dtype
-        self.channels_last = bool(channels_last)
-        B, D, H, W1, W2 = _check_fmaps(fmap1, fmap2)
-        self._shape = (B, H, W1, W2)
-        self._chain, self._shadow = True, frozenset()
-        grad = torch.is_grad_enabled() and (fmap1.requires_grad or fmap2.requires_grad)
-        with torch.no_grad():
-            self._records = build_records(fmap1, fmap2)
-        self._levels = [None] * (num_levels + 1)
-        self._state = self._token = None
-        if grad:
-            self._state = _GradState(B * H * W1, [W2 >> i for i in range(num_levels)], fmap1.device,
-                                     num_levels, radius, None, deferred=grad_deferred)
+        if torch.is_grad_enabled() and (fmap1.requires_grad or fmap2.requires_grad):
+            self._state = _GradState(B * H * W1, [W2 >> i for i in range(L)], fmap1.device, L, self.radius,
+                                     grad_shadow, deferred=grad_deferred, exact_f32=exact_f32)
             self._token = _BuildFn.apply(fmap1, fmap2, self._state)
 
     @property
@@ -1339,20 +1257,33 @@ class CorrBlock1D:
             return self._levels[:L]
         return self.corr_pyramid[:L]
 
+    def _source(self):
+        """What the lookups read: ``(pixel rows, device, keyword arguments of
+        _lookup_args)``."""
+        if self._records is not None:
+            rec = self._records
+            return rec.shape[0], rec.device, dict(kind="records", store=rec, W2=self._shape[3])
+        if self._sheared is not None:
+            B, H, W1, W2 = self._shape
+            return B * H * W1, self._sheared[0].device, dict(kind="disparity", store=self._sheared, W1=W1, W2=W2)
+        if self._chain:
+            lv = self._levels
+            return lv[0].shape[0], lv[0].device, dict(kind="chain", store=lv, shadow=self._shadow)
+        lv = self._read_levels()
+        return lv[0].shape[0], lv[0].device, dict(kind="levels", store=lv)
+
     def _lookup(self, coords):
         od = _check_out_dtype(self.out_dtype)
-        if self._records is not None:
-            return lookup_records(self._records, coords, self.radius, self._shape[3], self.channels_last, od)
-        if self._chain and self._sheared is None:
-            return lookup_chain(self._levels, coords, self.num_levels, self.radius, self._shadow,
-                                self.channels_last, od)
-        # kernels that write fp32 only: the cast follows (memory format kept)
-        if self._sheared is not None:
-            out = lookup_sheared(self._sheared, coords, self.num_levels, self.radius, self._shape[3])
-        else:
-            out = lookup(self._read_levels(), coords, self.num_levels, self.radius)
-            if self.channels_last:
-                out = out.contiguous(memory_format=torch.channels_last)
+        if self._chain:
+            # the pair / records kernel writes channels-last and the out_dtype itself
+            direct = self._sheared is None and (
+                self._records is not None or _pair_layout(self._levels, self.num_levels))
+            return _chain_lookup(*self._source(), coords, self.num_levels, self.radius, direct,
+                                 self.channels_last, od)
+        # the per-level kernel writes fp32 only: the cast follows (memory format kept)
+        out = lookup(self._read_levels(), coords, self.num_levels, self.radius)
+        if self.channels_last:
+            out = out.contiguous(memory_format=torch.channels_last)
         return out if od is None else out.to(od)
 
     def __call__(self, coords):
@@ -1375,10 +1306,8 @@ class CorrBlock1D:
             raise RuntimeError("CorrBlock1D.lookup_step is inference-only")
         if self._sheared is not None:
             raise RuntimeError("CorrBlock1D.lookup_step: not available with layout='disparity'")
-        if self._records is not None:
-            _check_records_coords(self._records, coords1)
-        else:
-            _check_coords(self._levels, coords1)
+        rows, device, src = self._source()
+        _check_coords(coords1, rows, device)
         B, C2, H, W1 = coords1.shape
         if C2 != 2:
             raise RuntimeError("lookup_step: coords1 must be (B, 2, H, W1)")
@@ -1402,31 +1331,21 @@ class CorrBlock1D:
         L, r = self.num_levels, self.radius
         # the pair / records kernel serves the step: channels-last and the
         # out_dtype are written by the kernel; else fp32 NCHW, converted after
-        pair = self._chain and (self._records is not None or _pair_layout(self._levels, L))
-        cl = self.channels_last and pair
+        direct = self._chain and (self._records is not None or _pair_layout(self._levels, L))
+        cl = self.channels_last and direct
         od = _check_out_dtype(self.out_dtype)
-        corr = _lookup_out(B, L * (2 * r + 1), H, W1, c1.device, cl, od if pair else None)
-        if B * H * W1 == 0:
-            return (corr if od is None else corr.to(od)), new, flow
-        if self._records is not None:
-            ptrs, widths, lds = _records_args(self._records, self._shape[3])
-            dt = _lib.RC_BF16 | _lib.RC_LAYOUT_RECORDS
-        elif self._chain:
-            keep, ptrs, widths, lds, dt = _chain_args(self._levels, L, self._shadow)
-        else:
-            keep, ptrs, widths, lds, dt = _level_args(self._read_levels(), L)
-        if cl:
-            dt |= _lib.RC_OUT_CHANNELS_LAST
-        if pair:
-            dt |= _out_flag(od)
-        with torch.cuda.device(c1.device):
-            rc = _lib.lib().rc_corr_lookup_step(
-                ptrs, widths, lds, dt, L, r, int(self._chain), c1.data_ptr(),
-                d.data_ptr() if d is not None else None, new.data_ptr(), flow.data_ptr(),
-                B, H, W1, corr.data_ptr(), _stream(c1.device))
-        _lib.check(rc, "rc_corr_lookup_step")
-        if self.channels_last and not cl:
-            corr = corr.contiguous(memory_format=torch.channels_last)
+        corr = _lookup_out(B, L * (2 * r + 1), H, W1, c1.device, cl, od if direct else None)
+        if B * H * W1:
+            keep, ptrs, widths, lds, flags = _lookup_args(L, **src)
+            if cl:
+                flags |= _lib.RC_OUT_CHANNELS_LAST
+            if direct:
+                flags |= _out_flag(od)
+            _launch("rc_corr_lookup_step", c1.device, ptrs, widths, lds, flags, L, r, int(self._chain),
+                    c1.data_ptr(), d.data_ptr() if d is not None else None, new.data_ptr(), flow.data_ptr(),
+                    B, H, W1, corr.data_ptr())
+            if self.channels_last and not cl:
+                corr = corr.contiguous(memory_format=torch.channels_last)
         return (corr if od is None else corr.to(od)), new, flow
 
     def lookup_convc1(self, coords, weight, bias=None, relu=True, differentiable=False, out_dtype=None):
@@ -1475,16 +1394,13 @@ class CorrBlock1D:
         L, r = self.num_levels, self.radius
         if self._chain and _pair_layout(self._levels, L):
             # the stored levels as they are (None = derived in registers)
-            if differentiable and grad:
-                return _LookupConvFn.apply(self._token, coords.detach(), weight, bias, self._state,
-                                           self._levels, L, r, bool(relu), self._shadow, od)
-            return lookup_chain_convc1(self._levels, coords, L, r, weight, bias, relu, self._shadow, od)
-        levels = self._read_levels()
+            levels, shadow = self._levels, self._shadow
+        else:
+            levels, shadow = self._read_levels(), None
         if differentiable and grad:
             return _LookupConvFn.apply(self._token, coords.detach(), weight, bias, self._state, levels,
-                                       L, r, bool(relu), None, od)
-        out = lookup_convc1(levels, coords, L, r, weight, bias, relu)
-        return out if od is None else out.to(od)
+                                       L, r, bool(relu), shadow, od)
+        return _convc1_forward(levels, coords, L, r, weight, bias, relu, shadow is not None, shadow, od)
 
     @staticmethod
     def corr(fmap1, fmap2, exact_f32=False):
