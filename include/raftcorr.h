@@ -30,6 +30,11 @@
  *   rc_corr_lookup_backward, rc_corr_build_backward  the gradient of the
  *                   path to the feature maps (autograd of model.py:267-326),
  *                   SURVEY.md §8f rank 2.
+ *   rc_gru_gates, rc_gru_blend and their backwards  the elementwise glue of
+ *                   ConvGRU.forward (model.py:164-179) between its convolutions.
+ *   rc_gru_assemble the work in front of each ConvGRU call: pool2x and interp
+ *                   (model.py:182-186) and the concatenation of [h, x]
+ *                   (model.py:172-173), one launch, nothing in between stored.
  *
  * The reference has no FFI; its "operator API" is the duck-typed class bound
  * at model.py:366-367 and called at :376.  raft-stereo_amd/corr.py mirrors that
@@ -56,7 +61,8 @@ extern "C" {
  * argument that a version-13 caller never passes (a library from before it
  * answers RC_EINVAL "unknown dtype"), no entry point, flag or layout changed,
  * so the number did not move for it either.  rc_gru_gates / rc_gru_blend and
- * their backward entry points are additive in the same way. */
+ * their backward entry points are additive in the same way, and so is
+ * rc_gru_assemble. */
 #define RC_ABI_VERSION 13
 
 /* element types */
@@ -555,6 +561,52 @@ int rc_gru_gates_backward(const void *g_z, const void *g_rh, const void *z, cons
 int rc_gru_blend_backward(const void *g_out, const void *z, const void *q_pre, const void *cq, const void *h,
                           void *g_z, void *g_qpre, void *g_h,
                           const long *strides, int dtype, int N, int C, long HW, void *stream);
+
+/* The input assembly of a ConvGRU update (added within ABI v13, additive): the
+ * N x (sum of channels) x H x W buffer `dst` -- [h, x], or a channel slice of
+ * it -- filled by ONE launch from nparts sources.  Part i fills the next
+ * channels[i] channels of dst from src[i], an N x channels[i] x src_h[i] x
+ * src_w[i] array of element type src_dtype[i] with the element strides
+ * src_strides[4i .. 4i+3] (batch, channel, row, column), by mode[i]:
+ *   RC_PART_COPY      dst = (T)src; src_h x src_w is H x W.  Same type: the
+ *                     same bits for every non-NaN value.
+ *   RC_PART_POOL2X    F.avg_pool2d(src, 3, stride=2, padding=1): the sum of
+ *                     the window's in-image taps row by row from 0.0f, then a
+ *                     correctly rounded division by 9.0f (the padding is
+ *                     counted).  H = (src_h - 1) / 2 + 1, W likewise.
+ *   RC_PART_BILINEAR  F.interpolate(src, (H, W), mode="bilinear",
+ *                     align_corners=True), ATen's sequence: per axis with
+ *                     source size S and destination size D, scale = D > 1 ?
+ *                     (float)(S-1) / (float)(D-1) : 0, s = scale * i, i0 =
+ *                     (int)s, i1 = i0 + (i0 < S-1), l1 = s - i0, l0 = 1 - l1;
+ *                     l0h*(l0w*a + l1w*b) + l1h*(l0w*c + l1w*d).  Any src_h,
+ *                     src_w >= 1; the same size gives the source's values.
+ *   Arithmetic as for rc_gru_gates: fp32 on the widened inputs, every
+ *   operation rounded on its own, one rounding to dst_dtype at the store; the
+ *   same bits whatever the layouts and access widths.
+ *   dst: element type dst_dtype, strides dst_strides[0..3]; planar (column
+ *   stride 1 and row stride W) or interleaved (channel stride 1), anything
+ *   else is RC_EUNSUPPORTED.  The sources take any non-negative strides and
+ *   any of the three element types, each independently of dst.  Accesses are
+ *   16 bytes of dst per lane where every base, stride and length allows (an
+ *   interleaved dst: sources of channel stride 1 and channel counts that are
+ *   whole vectors; a planar one: W a whole number of vectors and copied
+ *   sources of column stride 1), else 8 bytes, else one element.
+ *   RC_EINVAL, naming the argument, before any launch: nparts outside
+ *   1..RC_GRU_MAX_PARTS, a null pointer (arrays, dst, src[i]), an unknown
+ *   dst_dtype / src_dtype[i] / mode[i], channels[i] < 1, src_h[i] or src_w[i]
+ *   < 1, a negative size or stride, a copied or pooled part whose size does
+ *   not give H x W, dst == src[i] (no operand may overlap dst), and with work
+ *   to do a pointer not aligned to its element size.  N, H or W == 0: RC_OK,
+ *   nothing launched.  More than 2^31 - 1 elements of dst: RC_EUNSUPPORTED.
+ *   All offsets are computed in 64 bits. */
+#define RC_GRU_MAX_PARTS 4
+#define RC_PART_COPY     0
+#define RC_PART_POOL2X   1
+#define RC_PART_BILINEAR 2
+int rc_gru_assemble(void *dst, const long *dst_strides, int dst_dtype, int N, int H, int W, int nparts,
+                    const void *const *src, const long *src_strides, const int *src_dtype, const int *mode,
+                    const int *channels, const int *src_h, const int *src_w, void *stream);
 
 #ifdef __cplusplus
 }

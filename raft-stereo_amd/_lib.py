@@ -27,6 +27,8 @@ RC_LAYOUT_RECORDS = 0x100000     # rc_corr_build / _lookup_chain / _lookup_step:
 RC_OUT_F16 = 0x40000             # rc_corr_lookup_chain / _lookup_step / _lookup_chain_conv: fp16 output (ABI v13)
 RC_OUT_BF16 = 0x200000           # ... bf16 output
 RC_REC_SLOTS, RC_REC_BYTES = 64, 128
+RC_GRU_MAX_PARTS = 4             # rc_gru_assemble: parts per call, and their modes
+RC_PART_COPY, RC_PART_POOL2X, RC_PART_BILINEAR = 0, 1, 2
 
 
 def rec_count(W2):
@@ -90,6 +92,9 @@ SIGNATURES = {
     "rc_gru_blend": (_i, [_vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_l), _i, _i, _i, _l, _vp]),
     "rc_gru_gates_backward": (_i, [_vp] * 9 + [ctypes.POINTER(_l), _i, _i, _i, _l, _vp]),
     "rc_gru_blend_backward": (_i, [_vp] * 8 + [ctypes.POINTER(_l), _i, _i, _i, _l, _vp]),
+    "rc_gru_assemble": (_i, [_vp, ctypes.POINTER(_l), _i, _i, _i, _i, _i, ctypes.POINTER(_vp), ctypes.POINTER(_l),
+                             ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i),
+                             ctypes.POINTER(_i), _vp]),
 }
 
 _lib = None

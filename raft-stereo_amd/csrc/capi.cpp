@@ -1015,3 +1015,90 @@ extern "C" int rc_gru_blend_backward(const void *g_out, const void *z, const voi
     const char *const names[8] = {"g_out", "z", "q_pre", "cq", "h", "g_z", "g_qpre", "g_h"};
     return gru_backward("rc_gru_blend_backward", ops, names, 8, 3, strides, dtype, N, C, HW, true, stream);
 }
+
+extern "C" int rc_gru_assemble(void *dst, const long *dst_strides, int dst_dtype, int N, int H, int W, int nparts,
+                               const void *const *src, const long *src_strides, const int *src_dtype,
+                               const int *mode, const int *channels, const int *src_h, const int *src_w,
+                               void *stream) {
+    g_err[0] = 0;
+    const char *who = "rc_gru_assemble";
+    auto known = [](int dt) { return dt == RC_F32 || dt == RC_F16 || dt == RC_BF16; };
+    if (nparts < 1 || nparts > RC_GRU_MAX_PARTS)
+        return fail(RC_EINVAL, "%s: nparts=%d outside 1..%d", who, nparts, RC_GRU_MAX_PARTS);
+    if (!dst) return fail(RC_EINVAL, "%s: null dst", who);
+    if (!dst_strides) return fail(RC_EINVAL, "%s: null dst_strides", who);
+    if (!src) return fail(RC_EINVAL, "%s: null src", who);
+    if (!src_strides) return fail(RC_EINVAL, "%s: null src_strides", who);
+    if (!src_dtype) return fail(RC_EINVAL, "%s: null src_dtype", who);
+    if (!mode) return fail(RC_EINVAL, "%s: null mode", who);
+    if (!channels) return fail(RC_EINVAL, "%s: null channels", who);
+    if (!src_h || !src_w) return fail(RC_EINVAL, "%s: null %s", who, src_h ? "src_w" : "src_h");
+    if (!known(dst_dtype))
+        return fail(RC_EINVAL, "%s: unknown dst_dtype %d (RC_F32, RC_F16 or RC_BF16)", who, dst_dtype);
+    if (N < 0 || H < 0 || W < 0) return fail(RC_EINVAL, "%s: bad shape N=%d H=%d W=%d", who, N, H, W);
+    for (int k = 0; k < 4; ++k)
+        if (dst_strides[k] < 0)
+            return fail(RC_EINVAL, "%s: negative stride in dst_strides (%ld, %ld, %ld, %ld)", who, dst_strides[0],
+                        dst_strides[1], dst_strides[2], dst_strides[3]);
+    rc::GruAsmArgs a;
+    long long C = 0;
+    for (int i = 0; i < nparts; ++i) {
+        const long *t = src_strides + 4 * i;
+        if (!src[i]) return fail(RC_EINVAL, "%s: null src[%d]", who, i);
+        if (!known(src_dtype[i]))
+            return fail(RC_EINVAL, "%s: unknown src_dtype[%d] = %d (RC_F32, RC_F16 or RC_BF16)", who, i,
+                        src_dtype[i]);
+        if (mode[i] != RC_PART_COPY && mode[i] != RC_PART_POOL2X && mode[i] != RC_PART_BILINEAR)
+            return fail(RC_EINVAL, "%s: unknown mode[%d] = %d (RC_PART_COPY, RC_PART_POOL2X or RC_PART_BILINEAR)",
+                        who, i, mode[i]);
+        if (channels[i] < 1) return fail(RC_EINVAL, "%s: channels[%d] = %d, at least 1", who, i, channels[i]);
+        if (t[0] < 0 || t[1] < 0 || t[2] < 0 || t[3] < 0)
+            return fail(RC_EINVAL, "%s: negative stride in src_strides of part %d (%ld, %ld, %ld, %ld)", who, i,
+                        t[0], t[1], t[2], t[3]);
+        if (src_h[i] < 1 || src_w[i] < 1)
+            return fail(RC_EINVAL, "%s: src_h[%d] x src_w[%d] = %d x %d, at least 1 x 1", who, i, i, src_h[i],
+                        src_w[i]);
+        if (mode[i] == RC_PART_COPY && H && W && (src_h[i] != H || src_w[i] != W))
+            return fail(RC_EINVAL, "%s: RC_PART_COPY part %d has src_h x src_w = %d x %d, dst %d x %d", who, i,
+                        src_h[i], src_w[i], H, W);
+        if (mode[i] == RC_PART_POOL2X && H && W &&
+            (H != (src_h[i] - 1) / 2 + 1 || W != (src_w[i] - 1) / 2 + 1))
+            return fail(RC_EINVAL, "%s: RC_PART_POOL2X part %d has src_h x src_w = %d x %d, which pools to "
+                        "%d x %d, dst is %d x %d", who, i, src_h[i], src_w[i], (src_h[i] - 1) / 2 + 1,
+                        (src_w[i] - 1) / 2 + 1, H, W);
+        if (src[i] == dst) return fail(RC_EINVAL, "%s: dst is src[%d] (dst must not alias a source)", who, i);
+        rc::GruPart &P = a.part[i];
+        P.p = src[i];
+        P.sn = t[0], P.sc = t[1], P.sh = t[2], P.sw = t[3];
+        P.c0 = (int)C, P.C = channels[i];
+        P.mode = mode[i], P.ek = src_dtype[i];
+        P.SH = src_h[i], P.SW = src_w[i];
+        P.scale_h = H > 1 ? (float)(src_h[i] - 1) / (float)(H - 1) : 0.0f;
+        P.scale_w = W > 1 ? (float)(src_w[i] - 1) / (float)(W - 1) : 0.0f;
+        C += channels[i];
+    }
+    for (int i = nparts; i < rc::kGruMaxParts; ++i) a.part[i] = rc::GruPart{};
+    for (int i = 0; i < rc::kGruMaxParts; ++i) a.cend[i] = i < nparts ? a.part[i].c0 + a.part[i].C : (int)C;
+    const bool planar = (W <= 1 || dst_strides[3] == 1) && (H <= 1 || dst_strides[2] == (long)W * dst_strides[3]);
+    const bool inter = C == 1 || dst_strides[1] == 1;
+    if (!planar && !inter)
+        return fail(RC_EUNSUPPORTED, "%s: dst_strides (%ld, %ld, %ld, %ld) are neither planar (column stride 1, "
+                    "row stride W) nor interleaved (channel stride 1)", who, dst_strides[0], dst_strides[1],
+                    dst_strides[2], dst_strides[3]);
+    if ((long long)N * H * W == 0) return RC_OK;
+    const long long lim = 0x7FFFFFFFLL;
+    if ((long long)N * H > lim || (long long)N * H * W > lim || (long long)N * H * W * C > lim)
+        return fail(RC_EUNSUPPORTED, "%s: N*C*H*W elements (N=%d C=%lld H=%d W=%d) exceed 2^31 - 1", who, N, C, H, W);
+    if (reinterpret_cast<uintptr_t>(dst) % (dst_dtype == RC_F32 ? 4u : 2u))
+        return fail(RC_EINVAL, "%s: dst is not aligned to its element size", who);
+    for (int i = 0; i < nparts; ++i)
+        if (reinterpret_cast<uintptr_t>(src[i]) % (src_dtype[i] == RC_F32 ? 4u : 2u))
+            return fail(RC_EINVAL, "%s: src[%d] is not aligned to its element size", who, i);
+    a.dst = dst;
+    a.dn = dst_strides[0], a.dc = dst_strides[1], a.dh = dst_strides[2], a.dw = dst_strides[3];
+    a.N = N, a.C = (int)C, a.H = H, a.W = W;
+    a.nparts = nparts;
+    a.J = a.units = 0;
+    return hip_rc(rc_launch_gru_assemble(a, dst_dtype, !planar, reinterpret_cast<hipStream_t>(stream)),
+                  "rc_gru_assemble: launch");
+}

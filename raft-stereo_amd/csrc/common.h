@@ -280,6 +280,29 @@ struct GruBwdArgs {
     uint32_t J, units;
 };
 
+// rc_gru_assemble (gru_inputs.hip): the [h, x] buffer filled from up to
+// kGruMaxParts sources, each copied, 3x3/2 average-pooled or bilinearly resized
+// into its channel range.  Strides in elements, (batch, channel, row, column).
+constexpr int kGruMaxParts = 4;
+enum : int { kPartCopy = 0, kPartPool2x = 1, kPartBilinear = 2 };
+struct GruPart {
+    const void *p;
+    long long sn, sc, sh, sw;
+    int c0, C;                // its channels of dst: [c0, c0 + C)
+    int mode, ek;             // kPart*, element kind
+    int SH, SW;               // source height and width
+    float scale_h, scale_w;   // bilinear: (S - 1) / (D - 1) per axis, 0 for D == 1
+};
+struct GruAsmArgs {
+    void *dst;
+    long long dn, dc, dh, dw;
+    int N, C, H, W;           // C: the channels of all parts
+    int nparts;
+    uint32_t J, units;        // set by the launcher: work units per pixel (interleaved) or row (planar), and in all
+    int cend[kGruMaxParts];   // c0 + C of part i; C of an absent one
+    GruPart part[kGruMaxParts];
+};
+
 // CUs of the device current at the first call, taken once: every GPU of a
 // node this project runs on is the same.  256 when the query fails.
 inline int device_cus() {
@@ -339,6 +362,9 @@ hipError_t rc_launch_volume_bwd(const rc::BuildBwdArgs &a, hipStream_t s);
 hipError_t rc_launch_gru(const rc::GruArgs &a, int ek, bool blend, hipStream_t s);
 // their backward kernels (gru_gates_bwd.hip)
 hipError_t rc_launch_gru_bwd(const rc::GruBwdArgs &a, int ek, bool blend, hipStream_t s);
+// the ConvGRU input assembly into a dst of element kind ek, planar or
+// interleaved (gru_inputs.hip); sets a.J and a.units
+hipError_t rc_launch_gru_assemble(rc::GruAsmArgs &a, int ek, bool interleaved, hipStream_t s);
 hipError_t rc_launch_convex_upsample(const float *flow, const float *mask, int N, int C, int H,
                                      int W, int factor, float *out, hipStream_t s);
 // grad_flow / grad_mask may be null (not computed); workspace is read only with grad_flow

@@ -23,6 +23,16 @@ the training route is asked for as well (``ConvGRU.fuse_backward``,
 convolutions and the concatenations ordinary autograd ops.  That route keeps
 the [h, x] buffer, which the first convolution saves, and concatenates
 [r*h, x] into a second one.
+
+The work in front of each call -- ``pool2x`` / ``interp`` of the neighbouring
+scales' states and the concatenation itself -- can join the inference route
+as one more launch (rc_gru_assemble; csrc/gru_inputs.hip): the caller hands
+``Pooled(src)`` / ``Resized(src, size)`` descriptors instead of the pooled /
+resized tensors, and with ``ConvGRU.fuse_inputs`` set
+(``RAFTStereo(fuse_gru_inputs=True)``) ``assemble`` fills the [h, x] buffer
+from h, the plain parts and the descriptors' sources, where all of them are
+in the buffer's memory format.  Every other route materialises the
+descriptors with the PyTorch ops first and runs as before.
 """
 import weakref
 
@@ -35,6 +45,73 @@ _CODES = {torch.float32: _lib.RC_F32, torch.float16: _lib.RC_F16, torch.bfloat16
 
 _ZR = weakref.WeakKeyDictionary()   # ConvGRU -> (weight, bias, C, tag): convz and convr stacked
 _ZR_CAST = weakref.WeakKeyDictionary()   # ConvGRU -> (stacked weight, dtype, weight cast, bias cast)
+
+
+_MODES = {"copy": _lib.RC_PART_COPY, "pool2x": _lib.RC_PART_POOL2X, "bilinear": _lib.RC_PART_BILINEAR}
+
+
+class _Lazy:
+    """A part of x that has not been computed yet: what ``assemble`` needs to
+    compute it (``src``, ``mode``) and what the checks need of the result."""
+    mode = None
+
+    def __init__(self, src):
+        if not isinstance(src, torch.Tensor) or src.dim() != 4:
+            raise TypeError(f"{type(self).__name__}: a 4-D tensor, not {type(src).__name__}")
+        self.src = src
+
+    dtype = property(lambda self: self.src.dtype)
+    device = property(lambda self: self.src.device)
+    requires_grad = property(lambda self: self.src.requires_grad)
+
+    def dim(self):
+        return 4
+
+    def size(self, d=None):
+        return self.shape if d is None else self.shape[d]
+
+
+class Pooled(_Lazy):
+    """``network.pool2x(src)``, not computed yet."""
+    mode = "pool2x"
+
+    @property
+    def shape(self):
+        N, C, H, W = self.src.shape
+        return torch.Size((N, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1))
+
+    def materialize(self):
+        from . import network
+        return network.pool2x(self.src)
+
+
+class Resized(_Lazy):
+    """``network.interp(src, dest)`` with ``size = dest.shape[2:]``, not computed yet."""
+    mode = "bilinear"
+
+    def __init__(self, src, size):
+        super().__init__(src)
+        self.out_size = tuple(int(v) for v in size)
+        if len(self.out_size) != 2:
+            raise ValueError(f"Resized: size {size!r}: (H, W)")
+
+    @property
+    def shape(self):
+        return torch.Size((*self.src.shape[:2], *self.out_size))
+
+    def materialize(self):
+        from . import network
+        # interp reads its second argument's spatial size only
+        return network.interp(self.src, torch.empty((0, 0, *self.out_size), device="meta"))
+
+
+def materialized(x_list):
+    """x_list with every descriptor replaced by its tensor (the PyTorch ops)."""
+    return tuple(x.materialize() if isinstance(x, _Lazy) else x for x in x_list)
+
+
+def _is_part(t):
+    return isinstance(t, (torch.Tensor, _Lazy))
 
 
 def _zr_conv(gru):
@@ -119,10 +196,13 @@ def why_not_fusable(gru, h, cz, cr, cq, *x_list, differentiable=False):
     """None when ``conv_gru_forward`` can stand in for ``ConvGRU.forward`` on
     these arguments, else the first reason why not, in words.
     ``differentiable``: for ``conv_gru_forward(differentiable=True)``, which
-    a gradient being recorded does not stop; every other condition holds."""
+    a gradient being recorded does not stop; every other condition holds.
+    A part of x may be a ``Pooled`` / ``Resized`` descriptor: it counts with
+    its result's shape and dtype."""
     state = (h, cz, cr, cq)
     tensors = state + tuple(x_list)
-    if not x_list or any(not isinstance(t, torch.Tensor) or t.dim() != 4 for t in tensors):
+    if not x_list or any(not isinstance(t, torch.Tensor) for t in state) or \
+            any(not _is_part(t) or t.dim() != 4 for t in tensors):
         return "h, cz, cr, cq and at least one part of x, all 4-D tensors"
     dt = h.dtype
     if dt not in _CODES:
@@ -272,6 +352,95 @@ def gru_blend_backward(g_out, z, q_pre, cq, h, g_z=None, g_qpre=None, g_h=None):
     return tuple(outs)
 
 
+def why_not_assemblable(parts, dtype, memory_format=torch.contiguous_format, out=None):
+    """None when ``assemble`` can fill the buffer from ``parts`` (tensors and
+    ``Pooled`` / ``Resized`` descriptors), else the first reason why not, in
+    words."""
+    parts = tuple(parts)
+    if not 1 <= len(parts) <= _lib.RC_GRU_MAX_PARTS:
+        return f"{len(parts)} parts: 1 to {_lib.RC_GRU_MAX_PARTS}"
+    if any(not _is_part(t) or t.dim() != 4 for t in parts):
+        return "parts that are not 4-D tensors or Pooled / Resized descriptors"
+    if dtype not in _CODES:
+        return f"dtype {dtype}: float32, float16 or bfloat16"
+    if any(t.dtype not in _CODES for t in parts):
+        return "a part that is not float32, float16 or bfloat16"
+    first = parts[0]
+    if any(t.shape[0] != first.shape[0] or t.shape[2:] != first.shape[2:] for t in parts):
+        return "parts whose batch or spatial sizes differ"
+    if any(t.shape[1] < 1 or min(_src(t).shape[2:]) < 1 for t in parts):
+        return "an empty part"
+    if torch.is_grad_enabled() and any(t.requires_grad for t in parts):
+        return "a gradient is being recorded (the assembly has no backward)"
+    if first.device.type != "cuda":
+        return f"the parts are on {first.device}: HIP devices only"
+    if any(t.device != first.device for t in parts):
+        return "parts on different devices"
+    if memory_format not in (torch.contiguous_format, torch.channels_last):
+        return f"memory_format {memory_format}: contiguous_format or channels_last"
+    if out is not None:
+        want = (first.shape[0], sum(t.shape[1] for t in parts), *first.shape[2:])
+        if not isinstance(out, torch.Tensor) or tuple(out.shape) != want or out.dtype != dtype \
+                or out.device != first.device:
+            return f"out is not a {dtype} tensor of shape {want} on the parts' device"
+        if not _classes(out):
+            return "out is neither planar nor interleaved"
+        if any(_src(t).data_ptr() == out.data_ptr() for t in parts):
+            return "out is one of the sources"
+    return None
+
+
+def _sources_fit(parts, cls):
+    """Whether every part's source is of the buffer's layout class, so that
+    ``assemble`` moves whole vectors.  It computes the same values from any
+    strides, but then one element per lane, and with gru08's NCHW motion
+    features in a channels_last network that lost end to end against
+    ``interp`` + ``torch.cat`` (``e2e_bf16_cl_any`` in
+    profiles/gru_inputs.json).  ``conv_gru_forward`` leaves such inputs to the
+    PyTorch ops unless ``gru.fuse_inputs == "any"`` asks for the launch
+    whatever the formats are (tools/e2e_probe.py measures with it)."""
+    return all(_classes(_src(t)) & cls for t in parts)
+
+
+def _src(t):
+    return t.src if isinstance(t, _Lazy) else t
+
+
+def assemble(parts, dtype, memory_format=torch.contiguous_format, out=None):
+    """The concatenation of ``parts`` along the channels as a ``dtype`` tensor
+    of ``memory_format``, one launch (rc_gru_assemble) on the current stream:
+    a tensor is copied (and cast), a ``Pooled`` / ``Resized`` descriptor is
+    computed from its source straight into its channels.  ``out``: the buffer
+    to fill (planar or interleaved; a channel slice of a larger one will do)
+    instead of a new one.  Returns the buffer.  No CPU fallback."""
+    parts = tuple(parts)
+    for i, t in enumerate(parts):
+        if _is_part(t) and t.device.type != "cuda":
+            raise RuntimeError(f"assemble: part {i} is on {t.device}; the kernel runs on HIP devices only "
+                               "(no CPU fallback)")
+    why = why_not_assemblable(parts, dtype, memory_format, out)
+    if why is not None:
+        raise ValueError(f"assemble: {why}")
+    first = parts[0]
+    N, _, H, W = first.shape
+    if out is None:
+        out = torch.empty((N, sum(t.shape[1] for t in parts), H, W), dtype=dtype, device=first.device,
+                          memory_format=memory_format)
+    srcs = [_src(t) for t in parts]
+    modes = [_MODES[t.mode] if isinstance(t, _Lazy) else _lib.RC_PART_COPY for t in parts]
+    n = len(parts)
+    with torch.cuda.device(first.device):
+        stream = torch.cuda.current_stream(first.device).cuda_stream or None
+        rc = _lib.lib().rc_gru_assemble(
+            out.data_ptr(), _lib.long_array(out.stride()), _CODES[dtype], N, H, W, n,
+            _lib.ptr_array([t.data_ptr() for t in srcs]), _lib.long_array([v for t in srcs for v in t.stride()]),
+            _lib.int_array([_CODES[t.dtype] for t in srcs]), _lib.int_array(modes),
+            _lib.int_array([t.shape[1] for t in srcs]), _lib.int_array([t.shape[2] for t in srcs]),
+            _lib.int_array([t.shape[3] for t in srcs]), stream)
+    _lib.check(rc, "rc_gru_assemble")
+    return out
+
+
 def _as_class(t, cls):
     """t itself when it fits a class of ``cls``, else a copy that does (a
     convolution that answered in another memory format than its input's)."""
@@ -362,18 +531,28 @@ def conv_gru_forward(gru, h, cz, cr, cq, *x_list, differentiable=False):
     ``differentiable``: where a gradient is being recorded for an input or a
     gate weight, record a first-order autograd graph whose glue is the two
     backward kernels (arguments that are ``fusable(differentiable=True)``);
-    with nothing to record this is the inference route."""
+    with nothing to record this is the inference route.  ``Pooled`` /
+    ``Resized`` parts of x: with ``gru.fuse_inputs`` set the inference route
+    computes them inside the launch that fills the [h, x] buffer
+    (``assemble``); otherwise, and on the training route, they are
+    materialised with the PyTorch ops before anything else."""
     cls = _common_class((h, cz, cr, cq))
     if not cls:
         raise ValueError("conv_gru_forward: h, cz, cr and cq share no layout class (see gru.fusable)")
     if differentiable and _records_grad(gru, (h, cz, cr, cq, *x_list)):
-        return _conv_gru_train(gru, h, cz, cr, cq, x_list, cls)
+        return _conv_gru_train(gru, h, cz, cr, cq, materialized(x_list), cls)
     dt = h.dtype
     N, C, H, W = h.shape
-    Cx = sum(x.shape[1] for x in x_list)
     fmt = torch.contiguous_format if "planar" in cls else torch.channels_last
-    hx = torch.empty((N, C + Cx, H, W), dtype=dt, device=h.device, memory_format=fmt)
-    torch.cat([h, *x_list], dim=1, out=hx)
+    lazy = getattr(gru, "fuse_inputs", False)
+    if lazy and why_not_assemblable((h, *x_list), dt, fmt) is None \
+            and (lazy == "any" or _sources_fit(x_list, _one(cls))):
+        hx = assemble((h, *x_list), dt, fmt)            # pool2x, interp and the concatenation, one launch
+    else:
+        x_list = materialized(x_list)
+        Cx = sum(x.shape[1] for x in x_list)
+        hx = torch.empty((N, C + Cx, H, W), dtype=dt, device=h.device, memory_format=fmt)
+        torch.cat([h, *x_list], dim=1, out=hx)
     one = _one(cls)
     w, b, _ = _zr_conv_as(gru, dt)
     zr = _as_class(F.conv2d(hx, w, b, padding=gru.convz.padding, dilation=gru.convz.dilation), one)

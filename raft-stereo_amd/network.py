@@ -148,10 +148,17 @@ class ConvGRU(nn.Module):
     ``fuse_backward`` (the same kind of attribute; needs ``fuse``): where only
     the gradient being recorded stands in the way, take the fused route's
     differentiable form, whose backward runs the glue on two more kernels
-    (``gru.conv_gru_forward(differentiable=True)``)."""
+    (``gru.conv_gru_forward(differentiable=True)``).
+
+    ``fuse_inputs`` (the same kind of attribute; needs ``fuse``): on the fused
+    inference route fill the [h, x] buffer with one launch of
+    ``gru.assemble``, which also computes the parts of x handed over as
+    ``gru.Pooled`` / ``gru.Resized`` descriptors.  Every other route
+    materialises such descriptors with the PyTorch ops first."""
 
     fuse = False
     fuse_backward = False
+    fuse_inputs = False
 
     def __init__(self, hidden_dim, input_dim, kernel_size=3):
         super().__init__()
@@ -164,6 +171,7 @@ class ConvGRU(nn.Module):
             return _gru.conv_gru_forward(self, h, cz, cr, cq, *x_list)
         if self.fuse and self.fuse_backward and _gru.fusable(self, h, cz, cr, cq, *x_list, differentiable=True):
             return _gru.conv_gru_forward(self, h, cz, cr, cq, *x_list, differentiable=True)
+        x_list = _gru.materialized(x_list)
         x = torch.cat(x_list, dim=1)
         hx = torch.cat([h, x], dim=1)
         z = torch.sigmoid(self.convz(hx) + cz)
@@ -217,7 +225,14 @@ class FlowHead(nn.Module):
 
 
 class BasicMultiUpdateBlock(nn.Module):
-    """Three-scale GRU update (model.py:226-265).  ``net`` is updated in place."""
+    """Three-scale GRU update (model.py:226-265).  ``net`` is updated in place.
+
+    ``fuse_inputs`` (a plain attribute, off by default): hand the GRUs
+    ``gru.Pooled`` / ``gru.Resized`` descriptors of the neighbouring scales'
+    states instead of calling ``pool2x`` / ``interp``; ``ConvGRU.forward``
+    computes them, inside ``gru.assemble`` where it can."""
+
+    fuse_inputs = False
 
     def __init__(self, args, hidden_dims=()):
         super().__init__()
@@ -235,14 +250,18 @@ class BasicMultiUpdateBlock(nn.Module):
     def forward(self, net, inp, corr=None, flow=None, iter08=True, iter16=True, iter32=True,
                 update=True, corr_is_convc1=False):
         n = self.args.n_gru_layers
+        if self.fuse_inputs:
+            pool, resize = _gru.Pooled, lambda x, dest: _gru.Resized(x, dest.shape[2:])
+        else:
+            pool, resize = pool2x, interp
         if iter32:
-            net[2] = self.gru32(net[2], *inp[2], pool2x(net[1]))
+            net[2] = self.gru32(net[2], *inp[2], pool(net[1]))
         if iter16:
-            extra = (interp(net[2], net[1]),) if n > 2 else ()
-            net[1] = self.gru16(net[1], *inp[1], pool2x(net[0]), *extra)
+            extra = (resize(net[2], net[1]),) if n > 2 else ()
+            net[1] = self.gru16(net[1], *inp[1], pool(net[0]), *extra)
         if iter08:
             motion = self.encoder(flow, corr, corr_is_convc1)
-            extra = (interp(net[1], net[0]),) if n > 1 else ()
+            extra = (resize(net[1], net[0]),) if n > 1 else ()
             net[0] = self.gru08(net[0], *inp[0], motion, *extra)
         if not update:
             return net
@@ -253,7 +272,7 @@ class RAFTStereo(nn.Module):
     """model.py:335-383 with the correlation block pluggable (``corr_block``)."""
 
     def __init__(self, args, corr_block=None, fuse_convc1=False, fuse_step=False, corr_out_dtype=None,
-                 corr_pyramid_dtype=None, fuse_gru=False, fuse_gru_backward=False):
+                 corr_pyramid_dtype=None, fuse_gru=False, fuse_gru_backward=False, fuse_gru_inputs=False):
         super().__init__()
         self.args = args
         # corr_out_dtype (DESIGN.md §3.2j): the lookup output's dtype (with
@@ -307,6 +326,16 @@ class RAFTStereo(nn.Module):
         self.fuse_gru_backward = bool(fuse_gru_backward)
         for name in ("gru08", "gru16", "gru32"):
             getattr(self.update_block, name).fuse_backward = self.fuse_gru_backward
+        # fuse_gru_inputs: on the fused inference route pool2x, interp and the
+        # concatenation in front of each GRU are one launch (gru.assemble); the
+        # update block hands descriptors over instead of pooled / resized tensors.
+        # While a gradient is being recorded the PyTorch ops run as before.
+        if fuse_gru_inputs and not fuse_gru:
+            raise ValueError("RAFTStereo: fuse_gru_inputs=True needs fuse_gru=True")
+        self.fuse_gru_inputs = bool(fuse_gru_inputs)
+        self.update_block.fuse_inputs = self.fuse_gru_inputs
+        for name in ("gru08", "gru16", "gru32"):
+            getattr(self.update_block, name).fuse_inputs = self.fuse_gru_inputs
 
     def initialize_flow(self, img):
         N, _, H, W = img.shape

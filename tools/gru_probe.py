@@ -32,7 +32,23 @@ PyTorch ops it replaces, alternated in one process.
            to other jobs on one device -- in the settings of ``e2e``; host
            clock around synchronised steps.
 
+  inputs   the work in front of each ConvGRU call: pool2x / interp of the
+           neighbouring scales' states and ``torch.cat(out=)`` into the [h, x]
+           buffer (what conv_gru_forward runs without ``fuse_inputs``) against
+           one ``gru.assemble`` launch into the same buffer, at the three GRUs'
+           sizes and parts of config 2 (gru32: h, pool2x of the 68x120 state;
+           gru16: h, pool2x of the 135x240 state, interp of the 34x60 one;
+           gru08: h, the motion features -- fp32 in the bf16 rows, as under
+           autocast --, interp of the 68x120 state), fp32 and bf16, NCHW and
+           NHWC, and gru08 once more as a channels_last network has it: an
+           NHWC buffer with NCHW motion features, which the kernel takes one
+           element per lane.  Timing as ``kernels``.  The kernel's bytes (dst written
+           once, every source read once) over its time against the copy rate,
+           and the acceptance test of the change: the assembled side's median
+           against the torch side's median * (1 + its own (max - min) / median).
+
     python tools/gru_probe.py kernels [--out profiles/gru_gates.json]
+    python tools/gru_probe.py inputs [--out profiles/gru_inputs.json]
     python tools/gru_probe.py e2e --setting bf16 [--rounds 3]
     python tools/gru_probe.py train_kernels
     python tools/gru_probe.py train_step --setting bf16_cl [--rounds 3]
@@ -137,6 +153,66 @@ def kernels_part(reps, rounds):
                     row[k]["TB_per_s"] = rate / 1e12
                     row[k]["of_copy_rate"] = rate / COPY_RATE
                 row["speedup"] = row["torch_glue"]["median_us"] / row["fused_glue"]["median_us"]
+                print(json.dumps(row), flush=True)
+                rows.append(row)
+    return {"reps": reps, "rounds": rounds, "copy_rate_TB_per_s": COPY_RATE / 1e12, "rows": rows}
+
+
+# (H, W) of h and the x parts of each GRU at config 2: plain (H x W), pooled
+# from and resized from a neighbouring scale's state
+INPUT_PARTS = {"gru08": ((135, 240), (("plain", (135, 240)), ("resize", (68, 120)))),
+               "gru16": ((68, 120), (("pool", (135, 240)), ("resize", (34, 60)))),
+               "gru32": ((34, 60), (("pool", (68, 120)),))}
+
+
+def inputs_part(reps, rounds):
+    from raft_stereo_amd import network
+    rows = []
+    N, C = 8, 128
+    for name, ((H, W), parts) in INPUT_PARTS.items():
+        for dt in (torch.float32, torch.bfloat16):
+            # the third layout is a channels_last network's gru08: its motion
+            # features are NCHW (they are concatenated with the NCHW flow)
+            for cl, crossed in ((False, False), (True, False)) + (((True, True),) if name == "gru08" else ()):
+                g = torch.Generator(device="cuda").manual_seed(0)
+                fmt = torch.channels_last if cl else torch.contiguous_format
+
+                def rnd(h, w, dtype, fmt=fmt):
+                    t = torch.randn(N, C, h, w, device="cuda", generator=g).to(dtype)
+                    return t.contiguous(memory_format=fmt)
+
+                h = torch.tanh(rnd(H, W, dt))
+                # the motion features carry the fp32 flow: fp32 under autocast
+                srcs = [rnd(sh, sw, torch.float32, torch.contiguous_format if crossed else fmt) if kind == "plain"
+                        else rnd(sh, sw, dt) for kind, (sh, sw) in parts]
+                hx = torch.empty((N, C * (1 + len(parts)), H, W), dtype=dt, device="cuda", memory_format=fmt)
+                hx2 = torch.empty_like(hx)
+                lazy = [t if kind == "plain" else gru.Pooled(t) if kind == "pool" else gru.Resized(t, (H, W))
+                        for (kind, _), t in zip(parts, srcs)]
+
+                def torch_inputs():
+                    xs = [t if kind == "plain" else network.pool2x(t) if kind == "pool" else network.interp(t, h)
+                          for (kind, _), t in zip(parts, srcs)]
+                    return torch.cat([h, *xs], dim=1, out=hx)
+
+                def assembled():
+                    return gru.assemble([h, *lazy], dt, fmt, out=hx2)
+
+                with torch.no_grad():
+                    ms = alternate({"torch_inputs": torch_inputs, "assemble": assembled}, reps, rounds)
+                    err = (hx2.float() - hx.float()).abs().max().item() / hx.float().abs().max().item()
+                row = {"size": name, "shape": [N, C, H, W], "parts": [[k, list(s)] for k, s in parts],
+                       "dtype": str(dt).replace("torch.", ""), "layout": ("NHWC, NCHW motion" if crossed else "NHWC") if cl else "NCHW",
+                       "norm_err_vs_torch": err}
+                for k, v in ms.items():
+                    row[k] = summary(v)
+                nbytes = hx.numel() * hx.element_size() + sum(t.numel() * t.element_size() for t in [h] + srcs)
+                rate = nbytes / (row["assemble"]["median_us"] * 1e-6)
+                row["assemble"].update(bytes=nbytes, TB_per_s=rate / 1e12, of_copy_rate=rate / COPY_RATE)
+                base = row["torch_inputs"]
+                row["speedup"] = base["median_us"] / row["assemble"]["median_us"]
+                row["limit_us"] = base["median_us"] * (1 + (base["max_us"] - base["min_us"]) / base["median_us"])
+                row["within_limit"] = row["assemble"]["median_us"] <= row["limit_us"]
                 print(json.dumps(row), flush=True)
                 rows.append(row)
     return {"reps": reps, "rounds": rounds, "copy_rate_TB_per_s": COPY_RATE / 1e12, "rows": rows}
@@ -306,16 +382,20 @@ def e2e_part(setting, rounds, B=8, H=540, W=960, iters=32):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("part", choices=["kernels", "e2e", "train_kernels", "train_step"])
+    ap.add_argument("part", choices=["kernels", "inputs", "e2e", "train_kernels", "train_step"])
     ap.add_argument("--setting", choices=["fp32", "bf16", "bf16_cl"], default="bf16")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gru_gates.json"))
+    ap.add_argument("--out", default=None, help="profiles/gru_gates.json; profiles/gru_inputs.json for `inputs`")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "gru_inputs.json" if a.part == "inputs" else "gru_gates.json")
     if not torch.cuda.is_available():
         sys.exit("gru_probe: needs a HIP device (no CPU timing)")
     if a.part == "kernels":
         key, res = "kernels", kernels_part(a.reps, a.rounds or 7)
+    elif a.part == "inputs":
+        key, res = "inputs", inputs_part(a.reps, a.rounds or 7)
     elif a.part == "train_kernels":
         key, res = "train_kernels", train_kernels_part(a.reps, a.rounds or 7)
     elif a.part == "train_step":
