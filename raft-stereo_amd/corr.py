@@ -1069,7 +1069,13 @@ class CorrBlock1D:
         # (pinned by tests/test_split_gpu.py); with
         # check_finite=True one isfinite reduction over both fmaps (a host
         # sync) sends non-finite inputs to the exact fp32 kernel, with a
-        # warning, so the volume keeps the reference's +-inf entries
+        # warning, so the volume keeps the reference's +-inf entries.  The
+        # host has to read the reduction's result, which a stream that is
+        # being captured into a graph cannot give: refused before any launch
+        if check_finite and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("CorrBlock1D: check_finite=True inside a graph capture: the check reads its "
+                               "result on the host (a stream sync), which a capture does not allow; check "
+                               "the fmaps before capturing, or build with exact_f32=True")
         if (check_finite and not exact_f32 and fmap1.dtype == torch.float32 and
                 fmap2.dtype == torch.float32 and pyramid_dtype in (None, torch.float32)):
             if not (bool(torch.isfinite(fmap1).all()) and bool(torch.isfinite(fmap2).all())):

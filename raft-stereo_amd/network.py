@@ -339,7 +339,9 @@ class RAFTStereo(nn.Module):
 
     def initialize_flow(self, img):
         N, _, H, W = img.shape
-        return (coords_grid(N, H, W).to(img.device), coords_grid(N, H, W).to(img.device))
+        # built on the device: a grid made on the host and moved over is a
+        # pageable copy with a stream sync, which a graph capture refuses
+        return (coords_grid(N, H, W, device=img.device), coords_grid(N, H, W, device=img.device))
 
     def _autocast(self):
         enabled = bool(self.args.mixed_precision)
