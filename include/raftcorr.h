@@ -35,6 +35,8 @@
  *   rc_gru_assemble the work in front of each ConvGRU call: pool2x and interp
  *                   (model.py:182-186) and the concatenation of [h, x]
  *                   (model.py:172-173), one launch, nothing in between stored.
+ *   rc_gru_assemble_backward  its adjoint: the gradients of every part's source
+ *                   from the gradient(s) of the buffer, one launch, no atomics.
  *
  * The reference has no FFI; its "operator API" is the duck-typed class bound
  * at model.py:366-367 and called at :376.  raft-stereo_amd/corr.py mirrors that
@@ -62,7 +64,7 @@ extern "C" {
  * answers RC_EINVAL "unknown dtype"), no entry point, flag or layout changed,
  * so the number did not move for it either.  rc_gru_gates / rc_gru_blend and
  * their backward entry points are additive in the same way, and so is
- * rc_gru_assemble. */
+ * rc_gru_assemble with rc_gru_assemble_backward. */
 #define RC_ABI_VERSION 13
 
 /* element types */
@@ -607,6 +609,61 @@ int rc_gru_blend_backward(const void *g_out, const void *z, const void *q_pre, c
 int rc_gru_assemble(void *dst, const long *dst_strides, int dst_dtype, int N, int H, int W, int nparts,
                     const void *const *src, const long *src_strides, const int *src_dtype, const int *mode,
                     const int *channels, const int *src_h, const int *src_w, void *stream);
+
+/* The adjoint of rc_gru_assemble (added within ABI v13, additive): from the
+ * gradient of the assembled N x (sum of channels) x H x W buffer, the gradient
+ * of every part's source, ONE launch.
+ *   g: the gradient of the buffer, element type g_dtype, strides g_strides[0..3];
+ *   planar or interleaved exactly as dst of rc_gru_assemble, anything else is
+ *   RC_EUNSUPPORTED.  g2: NULL, or a second gradient of the same shape, strides
+ *   and type: part channels c >= g2_c0 then use G = g + g2, added in fp32 after
+ *   widening, the others G = g; g2 is never read below channel g2_c0 (one
+ *   launch for the gradients of [h, x] and of [r*h, x], whose first channels
+ *   belong to different tensors).
+ *   grad_src[i] receives the gradient of part i's source: N x channels[i] x
+ *   src_h[i] x src_w[i] elements of type grad_dtype[i] with the element strides
+ *   grad_strides[4i .. 4i+3], any non-negative ones.  NULL skips the part; its
+ *   channels still count, and its other entries are still checked.  Every
+ *   element of every other output is written: a source pixel that no
+ *   destination pixel reads (most pixels of a bilinear downscale) gets +0.
+ *   No atomics: each lane owns the elements it stores and every sum has a fixed
+ *   order, so the results repeat bit for bit and are the same whatever the
+ *   layouts and access widths.  Arithmetic as for rc_gru_assemble: fp32 on the
+ *   widened inputs, every operation rounded on its own, one rounding to
+ *   grad_dtype[i] at the store.  By mode[i]:
+ *   RC_PART_COPY      grad = (S)G.
+ *   RC_PART_POOL2X    source pixel (y, x) sums G over the windows that contain
+ *                     it: along H oy = y / 2 for even y, (y - 1) / 2 and
+ *                     (y + 1) / 2 for odd y, only oy < H; W likewise.  The sum
+ *                     is row-major from 0.0f, then one correctly rounded
+ *                     division by 9.0f.
+ *   RC_PART_BILINEAR  per axis the weight of destination index d on source
+ *                     index s is (i0(d) == s ? l0(d) : 0) + (i1(d) == s ? l1(d)
+ *                     : 0) with i0, i1, l0, l1 of rc_gru_assemble (where i1 ==
+ *                     i0 both terms land on the same pixel); grad = sum_dy
+ *                     wy(dy) * (sum_dx wx(dx) * G[dy][dx]), both sums ascending
+ *                     from 0.0f over the destinations with i0 in {s - 1, s}.
+ *                     Any sizes the forward accepts: a downscale, src_h or
+ *                     src_w == 1 and H or W == 1 (scale 0) included.
+ *   A unit of work is 16 bytes of g's element type along the unit-stride axis
+ *   of g's layout class, of one output, where every base, stride and length
+ *   allows (interleaved: outputs of channel stride 1, channel counts, channel
+ *   offsets and g2_c0 that are whole vectors; planar: outputs of column stride
+ *   1 and src_w a whole number of vectors), else 8 bytes, else one element;
+ *   outputs of the other layout class take the one-element path.
+ *   RC_EINVAL, naming the argument, before any launch: what rc_gru_assemble
+ *   refuses (g for dst, grad_src / grad_strides / grad_dtype for src /
+ *   src_strides / src_dtype; a NULL grad_src[i] is a skipped part), g2_c0
+ *   outside 0 .. sum of channels, an output that is g, g2 or another output (no
+ *   output may overlap a gradient or another output; equal base pointers are
+ *   caught), g2 == g, every grad_src[i] NULL.  RC_EUNSUPPORTED: g neither
+ *   planar nor interleaved; more than 2^31 - 1 elements in g or in an output.
+ *   N, H or W == 0: RC_OK, nothing launched.  All offsets are computed in 64
+ *   bits. */
+int rc_gru_assemble_backward(const void *g, const void *g2, int g2_c0, const long *g_strides, int g_dtype,
+                             int N, int H, int W, int nparts, void *const *grad_src, const long *grad_strides,
+                             const int *grad_dtype, const int *mode, const int *channels, const int *src_h,
+                             const int *src_w, void *stream);
 
 #ifdef __cplusplus
 }

@@ -95,6 +95,9 @@ SIGNATURES = {
     "rc_gru_assemble": (_i, [_vp, ctypes.POINTER(_l), _i, _i, _i, _i, _i, ctypes.POINTER(_vp), ctypes.POINTER(_l),
                              ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i),
                              ctypes.POINTER(_i), _vp]),
+    "rc_gru_assemble_backward": (_i, [_vp, _vp, _i, ctypes.POINTER(_l), _i, _i, _i, _i, _i, ctypes.POINTER(_vp),
+                                      ctypes.POINTER(_l), ctypes.POINTER(_i), ctypes.POINTER(_i),
+                                      ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), _vp]),
 }
 
 _lib = None

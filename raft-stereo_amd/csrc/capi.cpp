@@ -1102,3 +1102,107 @@ extern "C" int rc_gru_assemble(void *dst, const long *dst_strides, int dst_dtype
     return hip_rc(rc_launch_gru_assemble(a, dst_dtype, !planar, reinterpret_cast<hipStream_t>(stream)),
                   "rc_gru_assemble: launch");
 }
+
+extern "C" int rc_gru_assemble_backward(const void *g, const void *g2, int g2_c0, const long *g_strides, int g_dtype,
+                                        int N, int H, int W, int nparts, void *const *grad_src,
+                                        const long *grad_strides, const int *grad_dtype, const int *mode,
+                                        const int *channels, const int *src_h, const int *src_w, void *stream) {
+    g_err[0] = 0;
+    const char *who = "rc_gru_assemble_backward";
+    auto known = [](int dt) { return dt == RC_F32 || dt == RC_F16 || dt == RC_BF16; };
+    if (nparts < 1 || nparts > RC_GRU_MAX_PARTS)
+        return fail(RC_EINVAL, "%s: nparts=%d outside 1..%d", who, nparts, RC_GRU_MAX_PARTS);
+    if (!g) return fail(RC_EINVAL, "%s: null g", who);
+    if (!g_strides) return fail(RC_EINVAL, "%s: null g_strides", who);
+    if (!grad_src) return fail(RC_EINVAL, "%s: null grad_src", who);
+    if (!grad_strides) return fail(RC_EINVAL, "%s: null grad_strides", who);
+    if (!grad_dtype) return fail(RC_EINVAL, "%s: null grad_dtype", who);
+    if (!mode) return fail(RC_EINVAL, "%s: null mode", who);
+    if (!channels) return fail(RC_EINVAL, "%s: null channels", who);
+    if (!src_h || !src_w) return fail(RC_EINVAL, "%s: null %s", who, src_h ? "src_w" : "src_h");
+    if (!known(g_dtype)) return fail(RC_EINVAL, "%s: unknown g_dtype %d (RC_F32, RC_F16 or RC_BF16)", who, g_dtype);
+    if (N < 0 || H < 0 || W < 0) return fail(RC_EINVAL, "%s: bad shape N=%d H=%d W=%d", who, N, H, W);
+    for (int k = 0; k < 4; ++k)
+        if (g_strides[k] < 0)
+            return fail(RC_EINVAL, "%s: negative stride in g_strides (%ld, %ld, %ld, %ld)", who, g_strides[0],
+                        g_strides[1], g_strides[2], g_strides[3]);
+    if (g2 == g) return fail(RC_EINVAL, "%s: g2 is g (pass the sum's halves as two arrays, or g alone)", who);
+    rc::GruAsmBwdArgs a;
+    long long C = 0, most = 0;
+    int wanted = 0;
+    for (int i = 0; i < nparts; ++i) {
+        const long *t = grad_strides + 4 * i;
+        if (!known(grad_dtype[i]))
+            return fail(RC_EINVAL, "%s: unknown grad_dtype[%d] = %d (RC_F32, RC_F16 or RC_BF16)", who, i,
+                        grad_dtype[i]);
+        if (mode[i] != RC_PART_COPY && mode[i] != RC_PART_POOL2X && mode[i] != RC_PART_BILINEAR)
+            return fail(RC_EINVAL, "%s: unknown mode[%d] = %d (RC_PART_COPY, RC_PART_POOL2X or RC_PART_BILINEAR)",
+                        who, i, mode[i]);
+        if (channels[i] < 1) return fail(RC_EINVAL, "%s: channels[%d] = %d, at least 1", who, i, channels[i]);
+        if (t[0] < 0 || t[1] < 0 || t[2] < 0 || t[3] < 0)
+            return fail(RC_EINVAL, "%s: negative stride in grad_strides of part %d (%ld, %ld, %ld, %ld)", who, i,
+                        t[0], t[1], t[2], t[3]);
+        if (src_h[i] < 1 || src_w[i] < 1)
+            return fail(RC_EINVAL, "%s: src_h[%d] x src_w[%d] = %d x %d, at least 1 x 1", who, i, i, src_h[i],
+                        src_w[i]);
+        if (mode[i] == RC_PART_COPY && H && W && (src_h[i] != H || src_w[i] != W))
+            return fail(RC_EINVAL, "%s: RC_PART_COPY part %d has src_h x src_w = %d x %d, g %d x %d", who, i,
+                        src_h[i], src_w[i], H, W);
+        if (mode[i] == RC_PART_POOL2X && H && W &&
+            (H != (src_h[i] - 1) / 2 + 1 || W != (src_w[i] - 1) / 2 + 1))
+            return fail(RC_EINVAL, "%s: RC_PART_POOL2X part %d has src_h x src_w = %d x %d, which pools to "
+                        "%d x %d, g is %d x %d", who, i, src_h[i], src_w[i], (src_h[i] - 1) / 2 + 1,
+                        (src_w[i] - 1) / 2 + 1, H, W);
+        if (grad_src[i]) {
+            ++wanted;
+            if (grad_src[i] == g || grad_src[i] == g2)
+                return fail(RC_EINVAL, "%s: grad_src[%d] is %s (no output may overlap a gradient it is computed "
+                            "from)", who, i, grad_src[i] == g ? "g" : "g2");
+            for (int k = 0; k < i; ++k)
+                if (grad_src[k] == grad_src[i])
+                    return fail(RC_EINVAL, "%s: grad_src[%d] is grad_src[%d] (two outputs in one array)", who, i, k);
+            most = std::max(most, (long long)N * channels[i] * src_h[i] * src_w[i]);
+        }
+        rc::GruBwdPart &P = a.part[i];
+        P.p = grad_src[i];
+        P.sn = t[0], P.sc = t[1], P.sh = t[2], P.sw = t[3];
+        P.c0 = (int)C, P.C = channels[i];
+        P.mode = mode[i], P.ek = grad_dtype[i];
+        P.SH = src_h[i], P.SW = src_w[i];
+        P.scale_h = H > 1 ? (float)(src_h[i] - 1) / (float)(H - 1) : 0.0f;
+        P.scale_w = W > 1 ? (float)(src_w[i] - 1) / (float)(W - 1) : 0.0f;
+        P.J = 1, P.u0 = 0;
+        C += channels[i];
+    }
+    for (int i = nparts; i < rc::kGruMaxParts; ++i) a.part[i] = rc::GruBwdPart{};
+    if (!wanted) return fail(RC_EINVAL, "%s: every grad_src[i] is null (nothing to compute)", who);
+    if (g2_c0 < 0 || g2_c0 > C) return fail(RC_EINVAL, "%s: g2_c0=%d outside 0..%lld", who, g2_c0, C);
+    const bool planar = (W <= 1 || g_strides[3] == 1) && (H <= 1 || g_strides[2] == (long)W * g_strides[3]);
+    const bool inter = C == 1 || g_strides[1] == 1;
+    if (!planar && !inter)
+        return fail(RC_EUNSUPPORTED, "%s: g_strides (%ld, %ld, %ld, %ld) are neither planar (column stride 1, "
+                    "row stride W) nor interleaved (channel stride 1)", who, g_strides[0], g_strides[1],
+                    g_strides[2], g_strides[3]);
+    if ((long long)N * H * W == 0) return RC_OK;
+    const long long lim = 0x7FFFFFFFLL;
+    if ((long long)N * H > lim || (long long)N * H * W > lim || (long long)N * H * W * C > lim)
+        return fail(RC_EUNSUPPORTED, "%s: N*C*H*W elements of g (N=%d C=%lld H=%d W=%d) exceed 2^31 - 1", who, N, C,
+                    H, W);
+    if (most > lim)
+        return fail(RC_EUNSUPPORTED, "%s: an output of %lld elements exceeds 2^31 - 1", who, most);
+    const uintptr_t ges = g_dtype == RC_F32 ? 4u : 2u;
+    if (reinterpret_cast<uintptr_t>(g) % ges) return fail(RC_EINVAL, "%s: g is not aligned to its element size", who);
+    if (reinterpret_cast<uintptr_t>(g2) % ges)
+        return fail(RC_EINVAL, "%s: g2 is not aligned to its element size", who);
+    for (int i = 0; i < nparts; ++i)
+        if (reinterpret_cast<uintptr_t>(grad_src[i]) % (grad_dtype[i] == RC_F32 ? 4u : 2u))
+            return fail(RC_EINVAL, "%s: grad_src[%d] is not aligned to its element size", who, i);
+    a.g = g, a.g2 = g2;
+    a.gn = g_strides[0], a.gc = g_strides[1], a.gh = g_strides[2], a.gw = g_strides[3];
+    a.g2_c0 = g2_c0;
+    a.N = N, a.C = (int)C, a.H = H, a.W = W;
+    a.nparts = nparts;
+    a.units = 0;
+    return hip_rc(rc_launch_gru_assemble_bwd(a, g_dtype, !planar, reinterpret_cast<hipStream_t>(stream)),
+                  "rc_gru_assemble_backward: launch");
+}

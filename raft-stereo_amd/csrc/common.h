@@ -303,6 +303,31 @@ struct GruAsmArgs {
     GruPart part[kGruMaxParts];
 };
 
+// rc_gru_assemble_backward (gru_inputs_bwd.hip): the adjoint.  G = g (+ g2 from
+// channel g2_c0 on) is the gradient of the assembled buffer, part i's output
+// the gradient of its source.  A part without an output (p == nullptr) has no
+// units; its channels still count in c0.
+struct GruBwdPart {
+    void *p;
+    long long sn, sc, sh, sw;
+    int c0, C;                // its channels of G: [c0, c0 + C)
+    int mode, ek;             // kPart*, the output's element kind
+    int SH, SW;               // the output's (the source's) height and width
+    float scale_h, scale_w;   // as GruPart's
+    uint32_t J;               // set by the launcher: units per pixel (interleaved) or row (planar)
+    unsigned long long u0;    // set by the launcher: the part's first unit
+};
+struct GruAsmBwdArgs {
+    const void *g, *g2;       // g2 may be null
+    long long gn, gc, gh, gw;
+    int g2_c0;
+    int N, C, H, W;           // of G
+    int nparts;
+    unsigned long long units;                  // set by the launcher: all parts'
+    unsigned long long uend[kGruMaxParts];     // set by the launcher: u0 + units of part i
+    GruBwdPart part[kGruMaxParts];
+};
+
 // CUs of the device current at the first call, taken once: every GPU of a
 // node this project runs on is the same.  256 when the query fails.
 inline int device_cus() {
@@ -365,6 +390,8 @@ hipError_t rc_launch_gru_bwd(const rc::GruBwdArgs &a, int ek, bool blend, hipStr
 // the ConvGRU input assembly into a dst of element kind ek, planar or
 // interleaved (gru_inputs.hip); sets a.J and a.units
 hipError_t rc_launch_gru_assemble(rc::GruAsmArgs &a, int ek, bool interleaved, hipStream_t s);
+// its adjoint from a G of element kind ek (gru_inputs_bwd.hip); sets the unit counts of a
+hipError_t rc_launch_gru_assemble_bwd(rc::GruAsmBwdArgs &a, int ek, bool interleaved, hipStream_t s);
 hipError_t rc_launch_convex_upsample(const float *flow, const float *mask, int N, int C, int H,
                                      int W, int factor, float *out, hipStream_t s);
 // grad_flow / grad_mask may be null (not computed); workspace is read only with grad_flow

@@ -33,52 +33,9 @@
 //             l1 = s - i0, l0 = 1 - l1; l0h*(l0w*a + l1w*b) + l1h*(l0w*c + l1w*d).
 //             i0 is clamped to S - 1 (it never exceeds it by the formula; the
 //             clamp keeps every address in the image whatever scale holds).
-#include "gru_gates.h"    // GruPack, out_cvt, device_cus
+#include "gru_inputs.h"  // asm_ld1, asm_ldv, asm_axis, asm_clamp, asm_trips, asm_s
 
 namespace rc {
-
-// A source pointer as a global-memory one: a descriptor that went through
-// scalar registers (asm_scalar) no longer tells the compiler, which would
-// fall back to flat loads.
-#ifdef __HIP_DEVICE_COMPILE__
-#define ASM_GLOBAL __attribute__((address_space(1)))
-#else
-#define ASM_GLOBAL      // the host pass only parses the kernels
-#endif
-template <class S>
-__device__ __forceinline__ const ASM_GLOBAL S *asm_global(const void *p) {
-    return (const ASM_GLOBAL S *)reinterpret_cast<uintptr_t>(p);
-}
-
-template <class S>
-__device__ __forceinline__ float asm_ld1(const void *p, long long off) {
-    return (float)asm_global<S>(p)[off];
-}
-
-// V consecutive elements of type S as they are: one access of up to 16 bytes
-template <class S, int V>
-__device__ __forceinline__ GruPack<S, V> asm_ldv(const void *p, long long off) {
-    static_assert(sizeof(S) * V <= 16, "one access");
-    return *(const ASM_GLOBAL GruPack<S, V> *)(asm_global<S>(p) + off);
-}
-
-struct AsmAxis {
-    int i0, i1;
-    float l0, l1;
-};
-__device__ __forceinline__ AsmAxis asm_axis(float scale, int i, int S) {
-    const float s = scale * (float)i;
-    int i0 = (int)s;
-    i0 = i0 < S - 1 ? i0 : S - 1;
-    AsmAxis x;
-    x.i0 = i0;
-    x.i1 = i0 + (i0 < S - 1 ? 1 : 0);
-    x.l1 = s - (float)i0;
-    x.l0 = 1.0f - x.l1;
-    return x;
-}
-
-__device__ __forceinline__ int asm_clamp(int i, int S) { return i < 0 ? 0 : (i < S ? i : S - 1); }
 
 // o as a shift register: element k of a planar unit enters at the top in pass
 // k of a rolled loop, so after V passes it sits at index k.  Static indices
@@ -90,15 +47,6 @@ __device__ __forceinline__ void asm_push(GruPack<T, V> &o, float v) {
     for (int k = 0; k + 1 < V; ++k) o.v[k] = o.v[k + 1];
     asm("" : "+v"(v));      // as out_cvt does for the 16-bit types: the passes stay one loop for fp32 too
     o.v[V - 1] = out_cvt<T>(v);
-}
-
-// V behind an opaque copy: the planar gather loops stay rolled (a loop of a
-// known short trip count is unrolled whatever the pragma says).
-template <int V>
-__device__ __forceinline__ int asm_trips() {
-    int v = V;
-    asm volatile("" : "+s"(v));
-    return v;
 }
 
 // One unit of part P, whose source holds elements of type S.  Interleaved:
@@ -188,21 +136,13 @@ __device__ __forceinline__ void asm_unit_t(const GruPart &P, int n, int c, int h
     }
 }
 
-// A descriptor picked by a wave-uniform index, moved to scalar registers (the
-// compiler loads a dynamically indexed kernel argument per lane).
-__device__ __forceinline__ int asm_s(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ long long asm_s(long long v) {
-    const unsigned lo = (unsigned)asm_s((int)(unsigned)v), hi = (unsigned)asm_s((int)((unsigned long long)v >> 32));
-    return (long long)((unsigned long long)hi << 32 | lo);
-}
 __device__ __forceinline__ GruPart asm_scalar(const GruPart &v) {
     GruPart P;
     P.p = reinterpret_cast<const void *>(asm_s((long long)reinterpret_cast<uintptr_t>(v.p)));
     P.sn = asm_s(v.sn), P.sc = asm_s(v.sc), P.sh = asm_s(v.sh), P.sw = asm_s(v.sw);
     P.c0 = asm_s(v.c0), P.C = asm_s(v.C), P.mode = asm_s(v.mode), P.ek = asm_s(v.ek);
     P.SH = asm_s(v.SH), P.SW = asm_s(v.SW);
-    P.scale_h = __builtin_bit_cast(float, asm_s(__builtin_bit_cast(int, v.scale_h)));
-    P.scale_w = __builtin_bit_cast(float, asm_s(__builtin_bit_cast(int, v.scale_w)));
+    P.scale_h = asm_s(v.scale_h), P.scale_w = asm_s(v.scale_w);
     return P;
 }
 

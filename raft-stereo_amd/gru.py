@@ -33,6 +33,14 @@ resized tensors, and with ``ConvGRU.fuse_inputs`` set
 from h, the plain parts and the descriptors' sources, where all of them are
 in the buffer's memory format.  Every other route materialises the
 descriptors with the PyTorch ops first and runs as before.
+
+The training route does the same with ``ConvGRU.fuse_inputs_backward`` set
+(``RAFTStereo(fuse_gru_inputs_backward=True)``): [h, x] and [r*h, x] are one
+``assemble`` launch each inside two more ``torch.autograd.Function``s, and
+the gradients of h and of every part's source come from one launch of the
+assembly's adjoint (rc_gru_assemble_backward; csrc/gru_inputs_bwd.hip,
+``assemble_backward``) instead of the backward of two concatenations, the
+casts, ``avg_pool2d``, ``interpolate`` and an accumulation add per part.
 """
 import weakref
 
@@ -352,10 +360,11 @@ def gru_blend_backward(g_out, z, q_pre, cq, h, g_z=None, g_qpre=None, g_h=None):
     return tuple(outs)
 
 
-def why_not_assemblable(parts, dtype, memory_format=torch.contiguous_format, out=None):
+def why_not_assemblable(parts, dtype, memory_format=torch.contiguous_format, out=None, differentiable=False):
     """None when ``assemble`` can fill the buffer from ``parts`` (tensors and
     ``Pooled`` / ``Resized`` descriptors), else the first reason why not, in
-    words."""
+    words.  ``differentiable``: for ``assemble(differentiable=True)``, which a
+    gradient being recorded does not stop (it cannot fill ``out`` then)."""
     parts = tuple(parts)
     if not 1 <= len(parts) <= _lib.RC_GRU_MAX_PARTS:
         return f"{len(parts)} parts: 1 to {_lib.RC_GRU_MAX_PARTS}"
@@ -370,8 +379,11 @@ def why_not_assemblable(parts, dtype, memory_format=torch.contiguous_format, out
         return "parts whose batch or spatial sizes differ"
     if any(t.shape[1] < 1 or min(_src(t).shape[2:]) < 1 for t in parts):
         return "an empty part"
-    if torch.is_grad_enabled() and any(t.requires_grad for t in parts):
+    recorded = torch.is_grad_enabled() and any(t.requires_grad for t in parts)
+    if recorded and not differentiable:
         return "a gradient is being recorded (the assembly has no backward)"
+    if recorded and out is not None:
+        return "a gradient is being recorded and out is given (autograd does not see a buffer filled in place)"
     if first.device.type != "cuda":
         return f"the parts are on {first.device}: HIP devices only"
     if any(t.device != first.device for t in parts):
@@ -406,21 +418,26 @@ def _src(t):
     return t.src if isinstance(t, _Lazy) else t
 
 
-def assemble(parts, dtype, memory_format=torch.contiguous_format, out=None):
+def assemble(parts, dtype, memory_format=torch.contiguous_format, out=None, differentiable=False):
     """The concatenation of ``parts`` along the channels as a ``dtype`` tensor
     of ``memory_format``, one launch (rc_gru_assemble) on the current stream:
     a tensor is copied (and cast), a ``Pooled`` / ``Resized`` descriptor is
     computed from its source straight into its channels.  ``out``: the buffer
     to fill (planar or interleaved; a channel slice of a larger one will do)
-    instead of a new one.  Returns the buffer.  No CPU fallback."""
+    instead of a new one.  Returns the buffer.  No CPU fallback.
+    ``differentiable``: where a gradient is being recorded for a part, the
+    result carries an autograd node whose backward is one launch of
+    ``assemble_backward``; it saves no tensor (the adjoint is linear)."""
     parts = tuple(parts)
     for i, t in enumerate(parts):
         if _is_part(t) and t.device.type != "cuda":
             raise RuntimeError(f"assemble: part {i} is on {t.device}; the kernel runs on HIP devices only "
                                "(no CPU fallback)")
-    why = why_not_assemblable(parts, dtype, memory_format, out)
+    why = why_not_assemblable(parts, dtype, memory_format, out, differentiable)
     if why is not None:
         raise ValueError(f"assemble: {why}")
+    if differentiable and torch.is_grad_enabled() and any(t.requires_grad for t in parts):
+        return _AssembleFn.apply(None, _kinds(parts), dtype, memory_format, *[_src(t) for t in parts])
     first = parts[0]
     N, _, H, W = first.shape
     if out is None:
@@ -439,6 +456,67 @@ def assemble(parts, dtype, memory_format=torch.contiguous_format, out=None):
             _lib.int_array([t.shape[3] for t in srcs]), stream)
     _lib.check(rc, "rc_gru_assemble")
     return out
+
+
+def _parts_meta(parts):
+    """What ``assemble_backward`` needs of each part: (mode, the source's
+    shape, the source's dtype)."""
+    return tuple((t.mode if isinstance(t, _Lazy) else "copy", tuple(_src(t).shape), t.dtype) for t in parts)
+
+
+def assemble_backward(g, parts_meta, skip=(), g2=None, g2_from=0):
+    """The gradients of the sources of ``assemble`` from the gradient ``g`` of
+    its result, one launch (rc_gru_assemble_backward) on the current stream.
+    ``parts_meta``: one (mode, source shape, source dtype) per part with mode
+    "copy", "pool2x" or "bilinear" (``_parts_meta``); ``skip``: the indices of
+    the parts whose gradient is not wanted (their channels still count).
+    ``g2``: a second gradient of g's shape, strides and dtype; the channels
+    from ``g2_from`` on use g + g2 (added in fp32).  g is planar or
+    interleaved.  Returns one tensor per part, None for a skipped one, each
+    in its source's dtype and g's memory format.  No CPU fallback."""
+    parts_meta = tuple(parts_meta)
+    for t, n in ((g, "g"), (g2, "g2")):
+        if t is None and n == "g2":
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"assemble_backward: {n} must be a torch.Tensor")
+        if t.device.type != "cuda":
+            raise RuntimeError(f"assemble_backward: {n} is on {t.device}; the kernel runs on HIP devices only "
+                               "(no CPU fallback)")
+    if g.dim() != 4 or g.dtype not in _CODES:
+        raise ValueError(f"assemble_backward: g of shape {tuple(g.shape)} and {g.dtype}: 4-D, float32, float16 or "
+                         "bfloat16")
+    if not 1 <= len(parts_meta) <= _lib.RC_GRU_MAX_PARTS:
+        raise ValueError(f"assemble_backward: {len(parts_meta)} parts: 1 to {_lib.RC_GRU_MAX_PARTS}")
+    if any(m not in _MODES or len(shape) != 4 or dt not in _CODES for m, shape, dt in parts_meta):
+        raise ValueError("assemble_backward: parts_meta holds (mode, 4-D source shape, float dtype) entries")
+    N, C, H, W = g.shape
+    if C != sum(shape[1] for _, shape, _ in parts_meta) or any(shape[0] != N for _, shape, _ in parts_meta):
+        raise ValueError(f"assemble_backward: g has shape {tuple(g.shape)}, the parts "
+                         f"{[shape for _, shape, _ in parts_meta]}")
+    if g2 is not None and (g2.shape != g.shape or g2.dtype != g.dtype or g2.device != g.device
+                           or g2.stride() != g.stride()):
+        raise ValueError("assemble_backward: g2 differs from g in shape, strides, dtype or device")
+    cls = _classes(g)
+    if not cls:
+        raise ValueError(f"assemble_backward: g is neither planar nor interleaved (strides {g.stride()})")
+    fmt = torch.contiguous_format if "planar" in cls else torch.channels_last
+    skip = set(skip)
+    outs = [None if i in skip else torch.empty(shape, dtype=dt, device=g.device, memory_format=fmt)
+            for i, (_, shape, dt) in enumerate(parts_meta)]
+    n = len(parts_meta)
+    with torch.cuda.device(g.device):
+        stream = torch.cuda.current_stream(g.device).cuda_stream or None
+        rc = _lib.lib().rc_gru_assemble_backward(
+            g.data_ptr(), None if g2 is None else g2.data_ptr(), int(g2_from), _lib.long_array(g.stride()),
+            _CODES[g.dtype], N, H, W, n, _lib.ptr_array([None if t is None else t.data_ptr() for t in outs]),
+            _lib.long_array([v for t in outs for v in ((0, 0, 0, 0) if t is None else t.stride())]),
+            _lib.int_array([_CODES[dt] for _, _, dt in parts_meta]), _lib.int_array([_MODES[m] for m, _, _ in parts_meta]),
+            _lib.int_array([shape[1] for _, shape, _ in parts_meta]),
+            _lib.int_array([shape[2] for _, shape, _ in parts_meta]),
+            _lib.int_array([shape[3] for _, shape, _ in parts_meta]), stream)
+    _lib.check(rc, "rc_gru_assemble_backward")
+    return outs
 
 
 def _as_class(t, cls):
@@ -497,6 +575,78 @@ class _BlendFn(torch.autograd.Function):
         return g_z, g_qpre, g_qpre, g_h
 
 
+class _Call:
+    """What the two assembly nodes of one training call share: the gradient
+    of [r*h, x] on its way from ``_TailFn.backward`` to ``_AssembleFn.backward``."""
+    g_rx = None
+
+
+def _kinds(parts):
+    """The parts without their tensors: (mode, output size) each."""
+    return tuple((t.mode, t.shape[2:]) if isinstance(t, _Lazy) else ("copy", None) for t in parts)
+
+
+def _class_of(fmt):
+    return {"planar"} if fmt == torch.contiguous_format else {"interleaved"}
+
+
+class _AssembleFn(torch.autograd.Function):
+    """(the parts' sources) -> the assembled buffer on rc_gru_assemble; the
+    backward is one rc_gru_assemble_backward launch.  Saves no tensor: shapes,
+    dtypes and modes only.  With a ``call`` (the training route of
+    ``conv_gru_forward``) part 0 is h: its gradient is the first channels of
+    the incoming one, and the gradient that ``_TailFn.backward`` left in
+    ``call`` joins the other parts' inside the launch."""
+
+    @staticmethod
+    def forward(ctx, call, kinds, dtype, fmt, *sources):
+        parts = [t if m == "copy" else (Pooled(t) if m == "pool2x" else Resized(t, size))
+                 for t, (m, size) in zip(sources, kinds)]
+        ctx.call, ctx.meta, ctx.fmt = call, _parts_meta(parts), fmt
+        return assemble(parts, dtype, fmt)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        call, meta = ctx.call, ctx.meta
+        g = _as_class(g, _class_of(ctx.fmt))
+        g2, C = None, 0
+        skip = {i for i in range(len(meta)) if not ctx.needs_input_grad[4 + i]}
+        if call is not None:
+            g2, call.g_rx = call.g_rx, None         # dropped after use: a second backward stores it again
+            C = meta[0][1][1]
+            skip.add(0)
+            if g2 is not None and g2.stride() != g.stride():
+                g, g2 = g.contiguous(memory_format=ctx.fmt), g2.contiguous(memory_format=ctx.fmt)
+        outs = [None] * len(meta)
+        if len(skip) < len(meta):
+            outs = assemble_backward(g, meta, skip, g2=g2, g2_from=C)
+        if call is not None and ctx.needs_input_grad[4]:
+            outs[0] = g[:, :C]
+        return (None, None, None, None, *outs)
+
+
+class _TailFn(torch.autograd.Function):
+    """(hx, rh) -> [r*h, x], the second buffer of the training route: one
+    rc_gru_assemble launch with two copied parts, rh and hx's x channels.  Its
+    backward hands rh its channels of the gradient and leaves the whole
+    gradient in ``call`` for ``_AssembleFn.backward``, which runs later (rx
+    depends on hx through the gate convolution as well) and adds the x
+    channels to its own inside its launch; hx gets nothing from here."""
+
+    @staticmethod
+    def forward(ctx, call, fmt, hx, rh):
+        ctx.call, ctx.fmt, ctx.C = call, fmt, rh.shape[1]
+        return assemble((rh, hx[:, ctx.C:]), hx.dtype, fmt)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        g = _as_class(g, _class_of(ctx.fmt))
+        ctx.call.g_rx = g
+        return None, None, None, g[:, :ctx.C]
+
+
 def _records_grad(gru, tensors):
     """Whether autograd would record a gradient for an input or a gate weight."""
     if not torch.is_grad_enabled():
@@ -509,17 +659,32 @@ def _conv_gru_train(gru, h, cz, cr, cq, x_list, cls):
     """The training route of ``conv_gru_forward``: every step an autograd
     node.  Each part is cast before the concatenation (``torch.cat(out=)``
     records no gradient), and [r*h, x] is a second buffer: the stacked
-    convolution has saved [h, x]."""
+    convolution has saved [h, x].  With ``gru.fuse_inputs_backward`` set, and
+    where ``assemble`` takes the parts and every source is of the buffer's
+    layout class (``_sources_fit``, the rule of the inference route), the two
+    buffers are one ``assemble`` launch each and their backward is one
+    ``assemble_backward`` launch (``_AssembleFn``, ``_TailFn``): no pooled,
+    resized or cast tensor, no concatenation and no accumulation add per part."""
     dt = h.dtype
     C = h.shape[1]
     one = _one(cls)
     fmt = torch.contiguous_format if "planar" in one else torch.channels_last
-    xs = [x.to(dt) for x in x_list]
-    hx = torch.cat([h, *xs], dim=1).contiguous(memory_format=fmt)
+    call = None
+    if getattr(gru, "fuse_inputs_backward", False) \
+            and why_not_assemblable((h, *x_list), dt, fmt, differentiable=True) is None \
+            and _sources_fit(x_list, one):
+        call = _Call()
+        hx = _AssembleFn.apply(call, _kinds((h, *x_list)), dt, fmt, h, *[_src(t) for t in x_list])
+    else:
+        xs = [x.to(dt) for x in materialized(x_list)]
+        hx = torch.cat([h, *xs], dim=1).contiguous(memory_format=fmt)
     w, b, _ = _zr_conv(gru)
     zr = _as_class(F.conv2d(hx, w, b, padding=gru.convz.padding, dilation=gru.convz.dilation), one)
     z, rh = _GatesFn.apply(zr, cz, cr, h)
-    rx = torch.cat([rh, *xs], dim=1).contiguous(memory_format=fmt)
+    if call is not None:
+        rx = _TailFn.apply(call, fmt, hx, rh)
+    else:
+        rx = torch.cat([rh, *xs], dim=1).contiguous(memory_format=fmt)
     q = _as_class(gru.convq(rx), one)
     return _BlendFn.apply(z, q, cq, h)
 
@@ -534,13 +699,15 @@ def conv_gru_forward(gru, h, cz, cr, cq, *x_list, differentiable=False):
     with nothing to record this is the inference route.  ``Pooled`` /
     ``Resized`` parts of x: with ``gru.fuse_inputs`` set the inference route
     computes them inside the launch that fills the [h, x] buffer
-    (``assemble``); otherwise, and on the training route, they are
-    materialised with the PyTorch ops before anything else."""
+    (``assemble``), and with ``gru.fuse_inputs_backward`` set so does the
+    training route, whose backward is then one ``assemble_backward`` launch;
+    otherwise they are materialised with the PyTorch ops before anything
+    else."""
     cls = _common_class((h, cz, cr, cq))
     if not cls:
         raise ValueError("conv_gru_forward: h, cz, cr and cq share no layout class (see gru.fusable)")
     if differentiable and _records_grad(gru, (h, cz, cr, cq, *x_list)):
-        return _conv_gru_train(gru, h, cz, cr, cq, materialized(x_list), cls)
+        return _conv_gru_train(gru, h, cz, cr, cq, x_list, cls)
     dt = h.dtype
     N, C, H, W = h.shape
     fmt = torch.contiguous_format if "planar" in cls else torch.channels_last

@@ -154,11 +154,17 @@ class ConvGRU(nn.Module):
     inference route fill the [h, x] buffer with one launch of
     ``gru.assemble``, which also computes the parts of x handed over as
     ``gru.Pooled`` / ``gru.Resized`` descriptors.  Every other route
-    materialises such descriptors with the PyTorch ops first."""
+    materialises such descriptors with the PyTorch ops first.
+
+    ``fuse_inputs_backward`` (the same kind of attribute; needs ``fuse`` and
+    ``fuse_backward``): the differentiable route fills [h, x] and [r*h, x]
+    with ``gru.assemble`` as well, and their backward is one launch of
+    ``gru.assemble_backward``, wherever the inference route would assemble."""
 
     fuse = False
     fuse_backward = False
     fuse_inputs = False
+    fuse_inputs_backward = False
 
     def __init__(self, hidden_dim, input_dim, kernel_size=3):
         super().__init__()
@@ -272,7 +278,8 @@ class RAFTStereo(nn.Module):
     """model.py:335-383 with the correlation block pluggable (``corr_block``)."""
 
     def __init__(self, args, corr_block=None, fuse_convc1=False, fuse_step=False, corr_out_dtype=None,
-                 corr_pyramid_dtype=None, fuse_gru=False, fuse_gru_backward=False, fuse_gru_inputs=False):
+                 corr_pyramid_dtype=None, fuse_gru=False, fuse_gru_backward=False, fuse_gru_inputs=False,
+                 fuse_gru_inputs_backward=False):
         super().__init__()
         self.args = args
         # corr_out_dtype (DESIGN.md §3.2j): the lookup output's dtype (with
@@ -336,6 +343,15 @@ class RAFTStereo(nn.Module):
         self.update_block.fuse_inputs = self.fuse_gru_inputs
         for name in ("gru08", "gru16", "gru32"):
             getattr(self.update_block, name).fuse_inputs = self.fuse_gru_inputs
+        # fuse_gru_inputs_backward: the same launch on the training route, and
+        # its adjoint (gru.assemble_backward) as the backward of pool2x, interp,
+        # the casts and both concatenations; training with all three options above.
+        if fuse_gru_inputs_backward and not (fuse_gru and fuse_gru_backward and fuse_gru_inputs):
+            raise ValueError("RAFTStereo: fuse_gru_inputs_backward=True needs fuse_gru=True, fuse_gru_backward=True "
+                             "and fuse_gru_inputs=True")
+        self.fuse_gru_inputs_backward = bool(fuse_gru_inputs_backward)
+        for name in ("gru08", "gru16", "gru32"):
+            getattr(self.update_block, name).fuse_inputs_backward = self.fuse_gru_inputs_backward
 
     def initialize_flow(self, img):
         N, _, H, W = img.shape

@@ -24,13 +24,24 @@ PyTorch ops it replaces, alternated in one process.
            keeps), convolutions excluded: the stacked z/r pre-activations and
            q_pre are leaves, and the gradients the convolutions would send
            into [h, x] and [r*h, x] are given tensors.  Same sizes, dtypes,
-           layouts and timing as ``kernels``.
+           layouts and timing as ``kernels``.  Then the assembly glue, forward
+           + backward, at the sizes and parts of ``inputs``: torch autograd of
+           pool2x / interp / the casts / the two concatenations ([h, x] and
+           [r*h, x], rh a leaf, the two buffers' gradients given tensors)
+           against the assembled training route's two Functions (two
+           ``gru.assemble`` launches, one ``gru.assemble_backward``); rows
+           under ``assembly_rows``, written to profiles/gru_inputs_backward.json
+           with the limit of ``inputs``.
   train_step  one training step (forward, loss on every prediction,
            backward) of RAFTStereo with and without the fused GRUs
            (fuse_gru + fuse_gru_backward toggled on one model, alternated), at
            B = 2, 320x720, 22 iterations -- a size whose activations fit next
            to other jobs on one device -- in the settings of ``e2e``; host
-           clock around synchronised steps.
+           clock around synchronised steps.  ``--toggle inputs_backward``:
+           fuse_gru + fuse_gru_backward + fuse_gru_inputs on both sides, with
+           and without fuse_gru_inputs_backward (key
+           ``train_step_inputs_backward_<setting>`` of
+           profiles/gru_inputs_backward.json, with the limit of ``inputs``).
 
   inputs   the work in front of each ConvGRU call: pool2x / interp of the
            neighbouring scales' states and ``torch.cat(out=)`` into the [h, x]
@@ -52,6 +63,8 @@ PyTorch ops it replaces, alternated in one process.
     python tools/gru_probe.py e2e --setting bf16 [--rounds 3]
     python tools/gru_probe.py train_kernels
     python tools/gru_probe.py train_step --setting bf16_cl [--rounds 3]
+    python tools/gru_probe.py train_kernels --only assembly
+    python tools/gru_probe.py train_step --setting bf16_cl --toggle inputs_backward
 
 Each part merges its results into the --out file under its own key.
 """
@@ -286,14 +299,83 @@ def train_kernels_part(reps, rounds):
     return {"reps": reps, "rounds": rounds, "copy_rate_TB_per_s": COPY_RATE / 1e12, "rows": rows}
 
 
-def train_step_part(setting, rounds, B=2, H=320, W=720, iters=22):
+def train_assembly_part(reps, rounds):
+    """The assembly glue of the training route, forward + backward."""
+    from raft_stereo_amd import network
+    rows = []
+    N, C = 8, 128
+    for name, ((H, W), parts) in INPUT_PARTS.items():
+        for dt in (torch.float32, torch.bfloat16):
+            for cl in (False, True):
+                g = torch.Generator(device="cuda").manual_seed(0)
+                fmt = torch.channels_last if cl else torch.contiguous_format
+
+                def rnd(ch, h, w, dtype, grad=True):
+                    t = torch.randn(N, ch, h, w, device="cuda", generator=g).to(dtype)
+                    return t.contiguous(memory_format=fmt).requires_grad_(grad)
+
+                h, rh = torch.tanh(rnd(C, H, W, dt, False)).requires_grad_(True), rnd(C, H, W, dt)
+                # the motion features carry the fp32 flow: fp32 under autocast
+                srcs = [rnd(C, sh, sw, torch.float32 if kind == "plain" else dt) for kind, (sh, sw) in parts]
+                leaves = [h, rh, *srcs]
+                K = C * (1 + len(parts))
+                g_hx, g_rx = rnd(K, H, W, dt, False), rnd(K, H, W, dt, False)
+                lazy = lambda: [t if kind == "plain" else gru.Pooled(t) if kind == "pool"    # noqa: E731
+                                else gru.Resized(t, (H, W)) for (kind, _), t in zip(parts, srcs)]
+
+                def step(forward):
+                    for t in leaves:
+                        t.grad = None
+                    torch.autograd.backward(list(forward()), [g_hx, g_rx])
+
+                def torch_glue():
+                    xs = [(t if kind == "plain" else network.pool2x(t) if kind == "pool"
+                           else network.interp(t, h)).to(dt) for (kind, _), t in zip(parts, srcs)]
+                    hx = torch.cat([h, *xs], dim=1).contiguous(memory_format=fmt)
+                    return hx, torch.cat([rh, *xs], dim=1).contiguous(memory_format=fmt)
+
+                def assembled():
+                    call = gru._Call()
+                    x = lazy()
+                    hx = gru._AssembleFn.apply(call, gru._kinds((h, *x)), dt, fmt, h, *srcs)
+                    return hx, gru._TailFn.apply(call, fmt, hx, rh)
+
+                meta = gru._parts_meta((h, *lazy()))
+                fns = {"torch_glue": lambda: step(torch_glue), "assembled": lambda: step(assembled),
+                       "assemble_backward": lambda: gru.assemble_backward(g_hx, meta, (0,), g2=g_rx, g2_from=C)}
+                ms = alternate(fns, reps, rounds)
+                step(torch_glue)
+                want = [t.grad.float().clone() for t in leaves]
+                step(assembled)
+                err = max(((t.grad.float() - w).abs().max() / w.abs().max()).item() for t, w in zip(leaves, want))
+                row = {"size": name, "shape": [N, C, H, W], "parts": [[k, list(s)] for k, s in parts],
+                       "dtype": str(dt).replace("torch.", ""), "layout": "NHWC" if cl else "NCHW",
+                       "grad_norm_err_vs_torch": err}
+                for k, v in ms.items():
+                    row[k] = summary(v)
+                # both gradients read once, every source's gradient written once
+                nbytes = 2 * g_hx.numel() * g_hx.element_size() + sum(t.numel() * t.element_size() for t in srcs)
+                rate = nbytes / (row["assemble_backward"]["median_us"] * 1e-6)
+                row["assemble_backward"].update(bytes=nbytes, TB_per_s=rate / 1e12, of_copy_rate=rate / COPY_RATE)
+                base = row["torch_glue"]
+                row["speedup"] = base["median_us"] / row["assembled"]["median_us"]
+                row["limit_us"] = base["median_us"] * (1 + (base["max_us"] - base["min_us"]) / base["median_us"])
+                row["within_limit"] = row["assembled"]["median_us"] <= row["limit_us"]
+                print(json.dumps(row), flush=True)
+                rows.append(row)
+    return {"reps": reps, "rounds": rounds, "copy_rate_TB_per_s": COPY_RATE / 1e12, "assembly_rows": rows}
+
+
+def train_step_part(setting, rounds, B=2, H=320, W=720, iters=22, toggle="fuse_gru"):
     mixed, bench, cl = {"fp32": (False, False, False), "bf16": (True, False, False),
                         "bf16_cl": (True, True, True)}[setting]
     torch.backends.cudnn.benchmark = bench
     torch.manual_seed(0)
     args = StereoArgs(mixed_precision=mixed)
     args.autocast_dtype = torch.bfloat16
-    model = RAFTStereo(args, fuse_gru=True, fuse_gru_backward=True).eval().cuda()
+    inputs = toggle == "inputs_backward"       # both sides fused and assembled; the new option toggled
+    model = RAFTStereo(args, fuse_gru=True, fuse_gru_backward=True, fuse_gru_inputs=inputs,
+                       fuse_gru_inputs_backward=inputs).eval().cuda()
     if cl:
         model = model.to(memory_format=torch.channels_last)
     grus = [getattr(model.update_block, n) for n in ("gru08", "gru16", "gru32")]
@@ -303,7 +385,10 @@ def train_step_part(setting, rounds, B=2, H=320, W=720, iters=22):
 
     def step(fuse):
         for m in grus:
-            m.fuse = m.fuse_backward = fuse
+            if inputs:
+                m.fuse_inputs_backward = fuse
+            else:
+                m.fuse = m.fuse_backward = fuse
         model.zero_grad(set_to_none=True)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -334,6 +419,11 @@ def train_step_part(setting, rounds, B=2, H=320, W=720, iters=22):
            "loss_unfused": last[False][1], "loss_fused": last[True][1],
            "grad_norm_err": ((gf - gu).abs().max() / gu.abs().max()).item()}
     res["fused_over_unfused"] = res["fused_median_ms"] / res["unfused_median_ms"]
+    if inputs:      # "unfused" is the parent side: the three options without the new one
+        res["toggle"] = "fuse_gru_inputs_backward"
+        res["limit_ms"] = res["unfused_median_ms"] * (1 + (max(ms[False]) - min(ms[False]))
+                                                      / res["unfused_median_ms"])
+        res["within_limit"] = res["fused_median_ms"] <= res["limit_ms"]
     print(json.dumps(res), flush=True)
     return res
 
@@ -386,29 +476,49 @@ def main():
     ap.add_argument("--setting", choices=["fp32", "bf16", "bf16_cl"], default="bf16")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=None)
-    ap.add_argument("--out", default=None, help="profiles/gru_gates.json; profiles/gru_inputs.json for `inputs`")
+    ap.add_argument("--only", choices=["gates", "assembly"], default=None,
+                    help="train_kernels: the gate glue or the assembly glue alone")
+    ap.add_argument("--toggle", choices=["fuse_gru", "inputs_backward"], default="fuse_gru",
+                    help="train_step: what the two sides differ in")
+    ap.add_argument("--out", default=None, help="profiles/gru_gates.json; profiles/gru_inputs.json for `inputs`; "
+                    "profiles/gru_inputs_backward.json for the assembly glue and --toggle inputs_backward")
     a = ap.parse_args()
+    new = (a.part == "train_kernels" and a.only == "assembly") or \
+        (a.part == "train_step" and a.toggle == "inputs_backward")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "gru_inputs.json" if a.part == "inputs" else "gru_gates.json")
+        a.out = os.path.join(ROOT, "profiles", "gru_inputs_backward.json" if new else
+                             "gru_inputs.json" if a.part == "inputs" else "gru_gates.json")
     if not torch.cuda.is_available():
         sys.exit("gru_probe: needs a HIP device (no CPU timing)")
     if a.part == "kernels":
         key, res = "kernels", kernels_part(a.reps, a.rounds or 7)
     elif a.part == "inputs":
         key, res = "inputs", inputs_part(a.reps, a.rounds or 7)
+    elif a.part == "train_kernels" and a.only == "assembly":
+        key, res = "train_kernels", train_assembly_part(a.reps, a.rounds or 7)
     elif a.part == "train_kernels":
         key, res = "train_kernels", train_kernels_part(a.reps, a.rounds or 7)
+        if a.only is None:       # the assembly rows go to their own file
+            save(os.path.join(ROOT, "profiles", "gru_inputs_backward.json"), "train_kernels",
+                 train_assembly_part(a.reps, a.rounds or 7))
+    elif a.part == "train_step" and a.toggle == "inputs_backward":
+        key, res = f"train_step_inputs_backward_{a.setting}", train_step_part(a.setting, a.rounds or 3,
+                                                                               toggle=a.toggle)
     elif a.part == "train_step":
         key, res = f"train_step_{a.setting}", train_step_part(a.setting, a.rounds or 3)
     else:
         key, res = f"e2e_{a.setting}", e2e_part(a.setting, a.rounds or 3)
+    save(a.out, key, res)
+
+
+def save(path, key, res):
     doc = {}
-    if os.path.exists(a.out):
-        with open(a.out) as fh:
+    if os.path.exists(path):
+        with open(path) as fh:
             doc = json.load(fh)
     doc[key] = res
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as fh:
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as fh:
         json.dump(doc, fh, indent=1)
         fh.write("\n")
 
