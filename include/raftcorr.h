@@ -27,6 +27,9 @@
  *                   produces.
  *   rc_convex_upsample_backward  its gradient with respect to flow and mask,
  *                   for a training loss on the full-resolution prediction.
+ *   rc_upsample_head  the same upsampler for an inference forward's last
+ *                   step: an fp32, fp16 or bf16 mask, NCHW or channels-last,
+ *                   scaled inside the kernel.
  *   rc_corr_lookup_backward, rc_corr_build_backward  the gradient of the
  *                   path to the feature maps (autograd of model.py:267-326),
  *                   SURVEY.md §8f rank 2.
@@ -64,7 +67,7 @@ extern "C" {
  * answers RC_EINVAL "unknown dtype"), no entry point, flag or layout changed,
  * so the number did not move for it either.  rc_gru_gates / rc_gru_blend and
  * their backward entry points are additive in the same way, and so is
- * rc_gru_assemble with rc_gru_assemble_backward. */
+ * rc_gru_assemble with rc_gru_assemble_backward, and rc_upsample_head. */
 #define RC_ABI_VERSION 13
 
 /* element types */
@@ -495,6 +498,37 @@ int rc_convex_upsample(const float *flow, const float *mask, int N, int C, int H
 int rc_convex_upsample_backward(const float *flow, const float *mask, const float *grad_out,
                                 int N, int C, int H, int W, int factor,
                                 float *grad_flow, float *grad_mask, float *workspace, void *stream);
+
+/* The upsampling head of an inference forward (added within ABI v13,
+ * additive: a caller that needs it checks for the symbol): rc_convex_upsample
+ * on the mask as the update block's last convolution wrote it,
+ *   out[n][c][f h + i][f w + j] = sum_k softmax_k(scale * mask[n][k f^2 + i f + j][h][w])
+ *                                 * f * flow[n][c][h + dy_k][w + dx_k].
+ *   mask: (N, 9 f^2, H, W) elements of mask_dtype (RC_F32, RC_F16 or RC_BF16),
+ *   addressed by mask_strides[0..2] = its (batch, channel, pixel) strides in
+ *   elements, pixel = h W + w.  Two layout classes: planar (pixel stride 1,
+ *   channel stride H W: NCHW, any batch stride) and interleaved (channel
+ *   stride 1, pixel stride 9 f^2: channels-last, any batch stride); a stride
+ *   along an axis of length 1 is ignored; anything else is RC_EUNSUPPORTED.
+ *   scale: applied in fp32 to the widened logit, rounded once.  0.25 is the
+ *   update block's factor (model.py:264); 1.0 gives rc_convex_upsample.
+ *   flow: fp32, pixel stride 1, flow_strides[0..1] = its (batch, channel)
+ *   strides in elements: the x-channel of an (N, 2, H, W) tensor passes as it
+ *   is.  out: fp32 contiguous (N, C, f H, f W), aligned to min(16, 4 f) bytes.
+ *   The result equals rc_convex_upsample on the fp32 contiguous mask
+ *   scale * (float)mask bit for bit (the same arithmetic, in the same order),
+ *   in both classes and at every access width: mask loads are 8 bytes per lane
+ *   (planar) or f elements per lane (interleaved) where the base, the batch
+ *   stride and H W allow, one element otherwise.  Non-finite logits behave as
+ *   rc_convex_upsample's.
+ *   RC_EINVAL: an unknown mask_dtype, N < 0, C < 1, H < 0, W < 0, a factor
+ *   other than 1, 2, 4, 8, a null stride array, a negative stride and, with
+ *   N*H*W > 0, a null pointer, flow or mask not aligned to its element, out
+ *   not aligned.  N*H*W == 0: RC_OK, nothing launched.  All checks run before
+ *   the launch. */
+int rc_upsample_head(const float *flow, const long *flow_strides, const void *mask,
+                     const long *mask_strides, int mask_dtype, float scale, int N, int C, int H, int W,
+                     int factor, float *out, void *stream);
 
 /* The elementwise glue of the ConvGRU update between its convolutions (added
  * within ABI v13), two memory-bound launches:

@@ -86,6 +86,8 @@ SIGNATURES = {
                                            _i, ctypes.POINTER(_vp), _vp]),
     "rc_convex_upsample": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "rc_convex_upsample_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "rc_upsample_head": (_i, [_vp, ctypes.POINTER(_l), _vp, ctypes.POINTER(_l), _i, ctypes.c_float, _i, _i, _i, _i,
+                              _i, _vp, _vp]),
     "rc_corr_build_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, ctypes.POINTER(_vp),
                                     ctypes.POINTER(_l), _i, _vp, _vp, _vp]),
     "rc_gru_gates": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_l), _i, _i, _i, _l, _vp]),

@@ -922,6 +922,42 @@ extern "C" int rc_convex_upsample_backward(const float *flow, const float *mask,
                   who, "launch");
 }
 
+extern "C" int rc_upsample_head(const float *flow, const long *flow_strides, const void *mask,
+                                const long *mask_strides, int mask_dtype, float scale, int N, int C, int H,
+                                int W, int factor, float *out, void *stream) {
+    g_err[0] = 0;
+    const char *who = "rc_upsample_head";
+    if (!known_kind(mask_dtype))
+        return fail(RC_EINVAL, "%s: unknown mask dtype %d (RC_F32, RC_F16 or RC_BF16)", who, mask_dtype);
+    if (N < 0 || C < 1 || H < 0 || W < 0)
+        return fail(RC_EINVAL, "%s: bad shape N=%d C=%d H=%d W=%d", who, N, C, H, W);
+    if (factor != 1 && factor != 2 && factor != 4 && factor != 8)
+        return fail(RC_EINVAL, "%s: factor %d (1, 2, 4 or 8)", who, factor);
+    if (!flow_strides || !mask_strides) return fail(RC_EINVAL, "%s: null stride array", who);
+    if (flow_strides[0] < 0 || flow_strides[1] < 0 || mask_strides[0] < 0 || mask_strides[1] < 0 ||
+        mask_strides[2] < 0)
+        return fail(RC_EINVAL, "%s: negative stride", who);
+    // the mask's layout class; a stride along an axis of length 1 is ignored
+    const long long HW = (long long)H * W, MC = 9LL * factor * factor;
+    const bool planar = (HW <= 1 || mask_strides[2] == 1) && (HW == 0 || mask_strides[1] == HW);
+    const bool inter = mask_strides[1] == 1 && (HW <= 1 || mask_strides[2] == MC);
+    if (!planar && !inter)
+        return fail(RC_EUNSUPPORTED, "%s: mask strides (%ld, %ld, %ld) are of neither layout class: planar "
+                    "(channel stride H*W, pixel stride 1) or interleaved (channel stride 1, pixel stride 9 f^2)",
+                    who, mask_strides[0], mask_strides[1], mask_strides[2]);
+    if ((long long)N * HW == 0) return RC_OK;
+    if (!flow || !mask || !out) return fail(RC_EINVAL, "%s: null pointer", who);
+    if (!elem_aligned(flow, RC_F32) || !elem_aligned(mask, mask_dtype))
+        return fail(RC_EINVAL, "%s: flow or mask is not aligned to its element size", who);
+    const int align = 4 * std::min(factor, 4);
+    if (reinterpret_cast<uintptr_t>(out) & (uintptr_t)(align - 1))
+        return fail(RC_EINVAL, "%s: out must be %d-byte aligned", who, align);
+    if ((long long)N * HW > (1LL << 36))
+        return fail(RC_EUNSUPPORTED, "%s: N*H*W = %lld pixels exceed 2^36", who, (long long)N * HW);
+    rc::HeadArgs a{flow, flow_strides[0], flow_strides[1], mask, mask_strides[0], scale, out, N, C, H, W, 0};
+    return hip_rc(rc_launch_upsample_head(a, mask_dtype, factor, !planar, hip_stream(stream)), who, "launch");
+}
+
 // ---- gru: the gates, the blend, the input assembly, and their backward ---------------------------------------------
 namespace {
 // The checks of rc_gru_gates / rc_gru_blend and their backward entry points on

@@ -328,6 +328,20 @@ struct GruAsmBwdArgs {
     GruBwdPart part[kGruMaxParts];
 };
 
+// rc_upsample_head (upsample_head.hip).  Strides in elements; the mask's other
+// two strides are its layout class's (planar: H W per channel, 1 per pixel;
+// interleaved: 1 and 9 f^2).
+struct HeadArgs {
+    const float *flow;
+    long long fsn, fsc;       // flow batch and channel strides (pixel stride 1)
+    const void *mask;
+    long long msn;            // mask batch stride
+    float scale;
+    float *out;               // [N][C][f H][f W]
+    int N, C, H, W;
+    long long groups;         // set by the launcher: lanes per sub-row
+};
+
 // CUs of the device current at the first call, taken once: every GPU of a
 // node this project runs on is the same.  256 when the query fails.
 inline int device_cus() {
@@ -398,3 +412,6 @@ hipError_t rc_launch_convex_upsample(const float *flow, const float *mask, int N
 hipError_t rc_launch_convex_upsample_bwd(const float *flow, const float *mask, const float *grad_out,
                                          int N, int C, int H, int W, int factor, float *grad_flow,
                                          float *grad_mask, float *workspace, hipStream_t s);
+// rc_upsample_head's kernel on a mask of element kind ek, planar or interleaved
+// (upsample_head.hip); picks the access width and sets a.groups
+hipError_t rc_launch_upsample_head(rc::HeadArgs &a, int ek, int factor, bool interleaved, hipStream_t s);

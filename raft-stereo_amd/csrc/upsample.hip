@@ -39,23 +39,9 @@
 // element is read once and every grad_mask element written once:
 // 4 (9 f^2 + f^2 C + C) bytes read and 4 (9 f^2 + C) written per
 // low-resolution pixel, plus 4 * 9 C each way through the workspace.
-#include "common.h"
+#include "convex.h"
 
 namespace rc {
-
-template <int F>
-__device__ __forceinline__ void store_row(float *dst, const float (&v)[F]) {
-    if constexpr (F == 4) {
-        *reinterpret_cast<f32x4 *>(dst) = f32x4{v[0], v[1], v[2], v[3]};
-    } else if constexpr (F == 8) {
-        *reinterpret_cast<f32x4 *>(dst) = f32x4{v[0], v[1], v[2], v[3]};
-        *reinterpret_cast<f32x4 *>(dst + 4) = f32x4{v[4], v[5], v[6], v[7]};
-    } else if constexpr (F == 2) {
-        *reinterpret_cast<f32x2 *>(dst) = f32x2{v[0], v[1]};
-    } else {
-        dst[0] = v[0];
-    }
-}
 
 template <int F>
 __global__ __launch_bounds__(256) void convex_upsample_kernel(const float *__restrict__ flow,
@@ -77,38 +63,16 @@ __global__ __launch_bounds__(256) void convex_upsample_kernel(const float *__res
     float wt[F][9];
 #pragma unroll
     for (int j = 0; j < F; ++j) {
-        float mx = -INFINITY;
 #pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            wt[j][k] = m[((long long)k * F * F + j) * HW];
-            mx = fmaxf(mx, wt[j][k]);
-        }
-        float sum = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            wt[j][k] = expf(wt[j][k] - mx);
-            sum += wt[j][k];
-        }
-        const float inv = 1.0f / sum;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) wt[j][k] *= inv;
+        for (int k = 0; k < 9; ++k) wt[j][k] = m[((long long)k * F * F + j) * HW];
+        convex_weights(wt[j]);
     }
     for (int c = 0; c < C; ++c) {
-        const float *fl = flow + ((long long)n * C + c) * HW;
         float nb[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            const int yy = h + k / 3 - 1, xx = w + k % 3 - 1;
-            nb[k] = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? (float)F * fl[(long long)yy * W + xx] : 0.0f;
-        }
+        convex_neighbours<F>(flow + ((long long)n * C + c) * HW, h, w, H, W, nb);
         float o[F];
 #pragma unroll
-        for (int j = 0; j < F; ++j) {
-            float acc = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) acc = fmaf(wt[j][k], nb[k], acc);
-            o[j] = acc;
-        }
+        for (int j = 0; j < F; ++j) o[j] = convex_combine(wt[j], nb);
         store_row<F>(out + ((long long)n * C + c) * per_img + (long long)(h * F + i) * WO + (long long)w * F, o);
     }
 }

@@ -14,7 +14,10 @@ D4 update-block args, D5 cat tuple, D6 out_channels, D7 radius kwarg) and the
 truncated loop (D8) is completed the way the golden generator completes it:
 y-flow zeroed, coordinates stepped, low-resolution flow appended, list
 returned.  Everything else -- the missing final ReLU in residual blocks, the
-never-applied dropout, the unused ``test_mode`` -- is kept.
+never-applied dropout -- is kept.  ``test_mode``, which the reference accepts
+and never reads, is RAFT-Stereo's inference contract here: the last
+low-resolution flow and its full-resolution upsampling, with the mask head
+run once (``RAFTStereo.forward``).
 
 ``args`` is any object with the seven attributes the reference reads
 (SURVEY.md §5): hidden_dims, n_downsample, n_gru_layers, corr_levels,
@@ -254,7 +257,11 @@ class BasicMultiUpdateBlock(nn.Module):
                                   nn.Conv2d(256, (factor ** 2) * 9, 1, padding=0))
 
     def forward(self, net, inp, corr=None, flow=None, iter08=True, iter16=True, iter32=True,
-                update=True, corr_is_convc1=False):
+                update=True, corr_is_convc1=False, want_mask=True):
+        """``want_mask``: True returns the 0.25-scaled mask (model.py:264);
+        False skips the mask head and returns None in its place; "raw" returns
+        the head's unscaled logits, for a consumer that applies the 0.25 itself
+        (``upsample.upsample_head``)."""
         n = self.args.n_gru_layers
         if self.fuse_inputs:
             pool, resize = _gru.Pooled, lambda x, dest: _gru.Resized(x, dest.shape[2:])
@@ -271,7 +278,25 @@ class BasicMultiUpdateBlock(nn.Module):
             net[0] = self.gru08(net[0], *inp[0], motion, *extra)
         if not update:
             return net
+        if want_mask is False:
+            return net, None, self.flow_head(net[0])
+        if isinstance(want_mask, str):
+            if want_mask != "raw":
+                raise ValueError(f"BasicMultiUpdateBlock: want_mask={want_mask!r}: True, False or 'raw'")
+            return net, self.mask(net[0]), self.flow_head(net[0])
         return net, 0.25 * self.mask(net[0]), self.flow_head(net[0])
+
+
+def _upsample_head_torch(flow, mask, factor, scale):
+    """``upsample.upsample_head`` restated on PyTorch ops, for tensors that are
+    not on a HIP device: softmax over the 9 taps of scale * mask, weighted sum
+    of factor * flow over the 3x3 neighbourhood (F.unfold pads with zeros)."""
+    N, C, H, W = flow.shape
+    m = (scale * mask.float()).reshape(N, 1, 9, factor, factor, H, W)
+    m = torch.softmax(m, dim=2)
+    nb = F.unfold(factor * flow.float(), [3, 3], padding=1).view(N, C, 9, 1, 1, H, W)
+    up = torch.sum(m * nb, dim=2)                       # (N, C, f, f, H, W)
+    return up.permute(0, 1, 4, 2, 5, 3).reshape(N, C, factor * H, factor * W)
 
 
 class RAFTStereo(nn.Module):
@@ -397,8 +422,20 @@ class RAFTStereo(nn.Module):
         ``upsample=True`` the full-resolution x-flow of each iteration through
         the convex upsampler (``upsample.convex_upsample``)
         using the update block's mask (model.py:238-241, :264); differentiable
-        when grad is enabled."""
+        when grad is enabled.
+
+        ``test_mode=True`` (inference only, ``iters >= 1``) returns the tuple
+        ``(flow_low, flow_up)`` instead: the last iteration's low-resolution
+        flow (N, 2, h, w) and its fp32 full-resolution x-flow (N, 1, H, W).
+        The mask head runs in the last iteration only, and its unscaled logits
+        go to ``upsample.upsample_head`` in their own dtype and layout."""
         a = self.args
+        if test_mode:
+            if torch.is_grad_enabled():
+                raise RuntimeError("RAFTStereo: test_mode=True is inference-only; call it under torch.no_grad() "
+                                   "(forward(upsample=True) is the differentiable route)")
+            if iters < 1:
+                raise ValueError(f"RAFTStereo: test_mode=True needs iters >= 1, got {iters}")
         fmap1, fmap2, net_list, inp_list = self.features(image1, image2)
         corr_kw = self._corr_kwargs()
         corr_fn = self.corr_block(fmap1, fmap2, radius=a.corr_radius, num_levels=a.corr_levels, **corr_kw)
@@ -437,9 +474,11 @@ class RAFTStereo(nn.Module):
                 if a.n_gru_layers >= 2 and a.slow_fast_gru:
                     net_list = self.update_block(net_list, inp_list, iter32=a.n_gru_layers == 3,
                                                  iter16=True, iter08=False, update=False)
+                # test_mode: the mask head only where its output is used
+                want_mask = True if not test_mode else "raw" if itr == iters - 1 else False
                 net_list, up_mask, delta_flow = self.update_block(
                     net_list, inp_list, corr, flow, iter32=a.n_gru_layers == 3,
-                    iter16=a.n_gru_layers >= 2, corr_is_convc1=fused)
+                    iter16=a.n_gru_layers >= 2, corr_is_convc1=fused, want_mask=want_mask)
             if upsample:
                 masks.append(up_mask)
             if step:
@@ -452,6 +491,15 @@ class RAFTStereo(nn.Module):
             delta[:, 1] = 0.0
             coords1 = coords1 + delta
             predictions.append(coords1 - coords0)
+        if test_mode:
+            # up_mask: the last iteration's logits, which pair with the
+            # prediction appended last (under fuse_step: after the loop)
+            flow_low = predictions[-1]
+            f = 2 ** a.n_downsample
+            if flow_low.device.type == "cuda":
+                from .upsample import upsample_head
+                return flow_low, upsample_head(flow_low[:, :1], up_mask, f, 0.25)
+            return flow_low, _upsample_head_torch(flow_low[:, :1], up_mask, f, 0.25)
         if upsample:
             from .upsample import convex_upsample
             f = 2 ** a.n_downsample

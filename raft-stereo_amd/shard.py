@@ -314,6 +314,10 @@ def _instance_norm_rows(y, lo, hi, group, eps):
 class RowShardedStereo:
     """Row-sharded RAFT-Stereo forward over ``world`` ranks (one per GPU).
 
+    ``RAFTStereo.forward(test_mode=True)`` (the mask head once per forward, the
+    upsampling head on ``upsample.upsample_head``) is out of scope here: the
+    sharded forward returns what it returned before.
+
     * Encoders (``shard_encoders=True``, default):
       each rank runs cnet, conv2 and the context convs on its own band of
       image rows -- its GRU slab (below) plus ``enc_margin`` rows at 1/f res

@@ -16,6 +16,16 @@ network), which ``fuse_gru_inputs=True`` leaves to the PyTorch ops; the key is
 ``e2e_SETTING_any``.
 
     python tools/e2e_probe.py --compare-inputs bf16_cl [--rounds 3] [--out profiles/gru_inputs.json]
+
+``--compare-test-mode SETTING`` times the three ways to a disparity on one
+model (built with ``fuse_gru`` and ``fuse_gru_inputs``): ``forward()``,
+``forward(upsample=True)`` and ``forward(test_mode=True)``, alternated the same
+way; ``limit_ms`` is the ``forward()`` route's median plus its own spread.  It
+also records the difference between the test-mode ``flow_up`` and the last
+prediction of ``upsample=True``.  Merged into ``--out`` (default
+``profiles/test_mode.json``) under ``e2e_SETTING``.
+
+    python tools/e2e_probe.py --compare-test-mode bf16_cl [--rounds 3]
 """
 import argparse
 import json
@@ -102,6 +112,51 @@ def compare_inputs(setting, rounds, B=8, H=540, W=960, iters=32, any_format=Fals
     return res
 
 
+def compare_test_mode(setting, rounds, B=8, H=540, W=960, iters=32):
+    """forward(), forward(upsample=True) and forward(test_mode=True) on one model."""
+    mixed, bench, cl = SETTINGS[setting]
+    model, img1, img2 = build(mixed, bench, cl, B, H, W, fuse_gru=True, fuse_gru_inputs=True)
+    routes = {"forward": {}, "upsample": {"upsample": True}, "test_mode": {"test_mode": True}}
+
+    def forward(route):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = model(img1, img2, iters=iters, **routes[route])[-1]
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    ms = {r: [] for r in routes}
+    with torch.no_grad():
+        last = {r: forward(r)[1] for r in routes}                        # warm-up: every shape of every route
+        for _ in range(rounds):
+            for r in routes:
+                t, last[r] = forward(r)
+                ms[r].append(t)
+    diff = (last["test_mode"].float() - last["upsample"].float()).abs()
+    base = ms["forward"]
+    med = statistics.median(base)
+    res = {"setting": setting, "mixed_bf16": mixed, "miopen_benchmark": bench, "channels_last": cl,
+           "fuse_gru": True, "fuse_gru_inputs": True, "shape": [B, H, W], "iters": iters, "rounds": rounds,
+           **{f"{r}_ms": ms[r] for r in routes}, **{f"{r}_median_ms": statistics.median(ms[r]) for r in routes},
+           "limit_ms": med * (1 + (max(base) - min(base)) / med),
+           "flow_up_mae_px": diff.mean().item(), "flow_up_max_px": diff.max().item()}
+    res["test_mode_over_forward"] = res["test_mode_median_ms"] / med
+    res["test_mode_over_upsample"] = res["test_mode_median_ms"] / res["upsample_median_ms"]
+    res["within_limit"] = res["test_mode_median_ms"] <= res["limit_ms"]
+    return res
+
+
+def merge(path, key, res):
+    doc = {}
+    if os.path.exists(path):
+        with open(path) as fh:
+            doc = json.load(fh)
+    doc[key] = res
+    with open(path, "w") as fh:
+        json.dump(doc, fh, indent=1)
+        fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=2)
@@ -110,21 +165,22 @@ def main():
     ap.add_argument("--compare-inputs", choices=sorted(SETTINGS), default=None, metavar="SETTING")
     ap.add_argument("--any-format", action="store_true", help="with --compare-inputs: fuse_inputs = 'any'")
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gru_inputs.json"))
+    ap.add_argument("--compare-test-mode", choices=sorted(SETTINGS), default=None, metavar="SETTING")
+    ap.add_argument("--out", default=None, help="default: profiles/gru_inputs.json, or profiles/test_mode.json "
+                    "with --compare-test-mode")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("e2e_probe: needs a HIP device (no CPU timing)")
+    if a.compare_test_mode:
+        res = compare_test_mode(a.compare_test_mode, a.rounds)
+        print(json.dumps(res), flush=True)
+        merge(a.out or os.path.join(ROOT, "profiles", "test_mode.json"), f"e2e_{a.compare_test_mode}", res)
+        return
     if a.compare_inputs:
         res = compare_inputs(a.compare_inputs, a.rounds, any_format=a.any_format)
         print(json.dumps(res), flush=True)
-        doc = {}
-        if os.path.exists(a.out):
-            with open(a.out) as fh:
-                doc = json.load(fh)
-        doc[f"e2e_{a.compare_inputs}" + ("_any" if a.any_format else "")] = res
-        with open(a.out, "w") as fh:
-            json.dump(doc, fh, indent=1)
-            fh.write("\n")
+        merge(a.out or os.path.join(ROOT, "profiles", "gru_inputs.json"),
+              f"e2e_{a.compare_inputs}" + ("_any" if a.any_format else ""), res)
         return
     flags = {k: True for k, on in (("fuse_gru", a.fuse_gru), ("fuse_gru_inputs", a.fuse_gru_inputs)) if on}
     for mixed, bench, cl in [(False, False, False), (False, True, False), (True, False, False),
